@@ -33,6 +33,14 @@ Reference parity: the train step is the full D4PG update of
 forwards, C51 categorical projection, cross-entropy critic loss +
 backward + Adam, policy loss + backward + Adam, target soft-update, PER
 priority writeback) — nothing is skipped inside the timed region.
+
+A plain run only sets up, warms up, times the K steps and prints the
+result line.  ``--dump-outputs DIR`` additionally writes rank 0's learner
+state after the last timed step (parameter slabs; on the GPU also the last
+critic distribution, action and priorities) as DIR/<name>.npy —
+seeds are fixed, so two builds can be compared output for output.
+``--full`` adds the auxiliary actor-side env-steps/s figures (CPU 1-actor,
+CPU vector64, GPU-resident rollout) to the result line.
 """
 
 from __future__ import annotations
@@ -207,7 +215,7 @@ def run_gpu_multirank(dist_mod, world, rank, args):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         _barrier(dist_mod)
-        return elapsed, "dp%d (sync grad all-reduce per step)" % world
+        return elapsed, "dp%d (sync grad all-reduce per step)" % world, eng
 
     if mode == "indep":
         spg = args.steps_per_graph
@@ -218,7 +226,8 @@ def run_gpu_multirank(dist_mod, world, rank, args):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         _barrier(dist_mod)
-        return elapsed, "indep%d (no communication; A/B baseline)" % world
+        return (elapsed, "indep%d (no communication; A/B baseline)" % world,
+                eng)
 
     # localsgd (default): bounded-staleness HogWild over RCCL
     sync = LocalSGDSync(eng)
@@ -244,13 +253,36 @@ def run_gpu_multirank(dist_mod, world, rank, args):
     elapsed = time.perf_counter() - t0
     _barrier(dist_mod)
     return elapsed, ("hogwild-rccl x%d (param avg + transition all_gather "
-                     "every %d steps)" % (world, S))
+                     "every %d steps)" % (world, S)), eng
+
+
+def collect_outputs(learner, use_gpu: bool) -> dict:
+    """What a caller of the timed path holds after its last step: the four
+    parameter slabs (engine slab layout, ops.pack_net) and, on the GPU
+    engine, the last step's critic distribution, policy action and PER
+    priorities (the loss counters are left out: they are atomic float
+    sums whose last bit varies run to run).  All float32, ~2.2 MB."""
+    names = ("actor", "actor_target", "critic", "critic_target")
+    if not use_gpu:
+        from d4pg_amd.ops import pack_net
+        return {n: pack_net(getattr(learner, n)).numpy() for n in names}
+    out = {n: learner.store_slab(n).numpy() for n in names}
+    for n in ("q", "a_out", "pri"):
+        out["last_" + n] = learner.read(n).numpy()
+    return out
+
+
+def dump_outputs(outdir: str, arrays: dict) -> None:
+    os.makedirs(outdir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"),
+                np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def measure_env_steps_per_sec(seed: int, n: int = 3000) -> float:
-    """Auxiliary (untimed-region) metric: actor-side env-steps/sec — native
-    Pendulum dynamics + B=1 actor inference + exploration noise, the per-env-
-    step path of /root/reference/main.py:142-152."""
+    """Auxiliary (untimed-region, --full only) metric: actor-side
+    env-steps/sec — native Pendulum dynamics + B=1 actor inference +
+    exploration noise, the reference's per-env-step actor loop."""
     from d4pg_amd.envs import make
     from d4pg_amd.models import actor
     from d4pg_amd.noise import GaussianNoise
@@ -311,6 +343,16 @@ def main():
     ap.add_argument("--xfer_transitions", type=int, default=1,
                     help="localsgd: all_gather+ingest a synthetic "
                          "transition block every sync round")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's learner "
+                         "state of the last timed step (parameter slabs, "
+                         "last critic distribution / action / priorities) "
+                         "as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the auxiliary actor-side figures "
+                         "(CPU 1-actor and vector64 env-steps/s, GPU "
+                         "rollout env-steps/s); a plain run only times "
+                         "the learner steps")
     args = ap.parse_args()
 
     dist, world, rank, local = _dist_init(args)
@@ -324,9 +366,10 @@ def main():
     K, W = args.steps, args.warmup
     parallelism = "dp1 (one learner per GPU)"
     if use_gpu and world > 1:
-        elapsed, parallelism = run_gpu_multirank(dist, world, rank, args)
+        elapsed, parallelism, learner = run_gpu_multirank(dist, world, rank,
+                                                          args)
     elif use_gpu:
-        eng = make_gpu_engine(seed=1000 + rank)
+        learner = eng = make_gpu_engine(seed=1000 + rank)
         spg = args.steps_per_graph
         eng.train_steps(max(W, spg), steps_per_graph=spg)  # warmup+capture
         _barrier(dist)
@@ -336,9 +379,7 @@ def main():
         elapsed = time.perf_counter() - t0
         _barrier(dist)
     else:
-        K = min(K, 400)
-        W = min(W, 20)
-        agent = make_cpu_agent(seed=1000 + rank)
+        learner = agent = make_cpu_agent(seed=1000 + rank)
         if world > 1:
             # CPU rehearsal of the multi-rank topology: eager agents with
             # per-step gradient averaging over gloo (parallel/dp.py hook)
@@ -355,22 +396,31 @@ def main():
         _barrier(dist)
 
     elapsed = _max_over_ranks(dist, elapsed)
-    env_sps = measure_env_steps_per_sec(seed=1234 + rank) if rank == 0 else 0.0
-    vec_sps = measure_env_steps_vector(seed=4321 + rank) if rank == 0 else 0.0
-    gpu_sps = None
-    if rank == 0 and use_gpu:
-        # device-resident actor serving (env + policy + noise + fold all
-        # on-GPU, engine.hip rollout section): M=8192 envs, 200-tick
-        # episodes, one hipGraph per episode.  Throughput keeps scaling
-        # with M (211M env-steps/s at M=65536, profiles/README.md); 8192
-        # is a practical per-actor-rank size.
-        eng2 = make_gpu_engine(seed=999)
-        eng2.rollout_alloc(8192, FLAGSHIP["n_steps"], horizon=200,
-                           gamma=FLAGSHIP["gamma"], eps=0.3, seed=555)
-        eng2.rollout_run(1)                       # capture + warm
-        t0 = time.perf_counter()
-        steps_done, _ = eng2.rollout_run(6)
-        gpu_sps = steps_done / (time.perf_counter() - t0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, collect_outputs(learner, use_gpu))
+
+    aux = {}
+    if rank == 0 and args.full:
+        # auxiliary actor-side figures, outside the headline measurement
+        aux["env_steps_per_sec_1actor"] = \
+            measure_env_steps_per_sec(seed=1234 + rank)
+        aux["env_steps_per_sec_vector64"] = \
+            measure_env_steps_vector(seed=4321 + rank)
+        gpu_sps = None
+        if use_gpu:
+            # device-resident actor serving (env + policy + noise + fold all
+            # on-GPU, engine.hip rollout section): M=8192 envs, 200-tick
+            # episodes, one hipGraph per episode.  Throughput keeps scaling
+            # with M (211M env-steps/s at M=65536, profiles/README.md); 8192
+            # is a practical per-actor-rank size.
+            eng2 = make_gpu_engine(seed=999)
+            eng2.rollout_alloc(8192, FLAGSHIP["n_steps"], horizon=200,
+                               gamma=FLAGSHIP["gamma"], eps=0.3, seed=555)
+            eng2.rollout_run(1)                       # capture + warm
+            t0 = time.perf_counter()
+            steps_done, _ = eng2.rollout_run(6)
+            gpu_sps = steps_done / (time.perf_counter() - t0)
+        aux["env_steps_per_sec_gpu_rollout8192"] = gpu_sps
 
     if rank == 0:
         # In every mode each rank performs K real optimizer steps, so the
@@ -404,10 +454,8 @@ def main():
                        "prioritized_replay": True,
                        "replay_capacity": FLAGSHIP["capacity"],
                        "device": "cuda" if use_gpu else "cpu-fallback"},
-            "env_steps_per_sec_1actor": env_sps,
-            "env_steps_per_sec_vector64": vec_sps,
-            "env_steps_per_sec_gpu_rollout8192": gpu_sps,
         }
+        out.update(aux)                 # --full only
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -10,15 +10,63 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_json_contract():
+AUX_KEYS = ("env_steps_per_sec_1actor", "env_steps_per_sec_vector64",
+            "env_steps_per_sec_gpu_rollout8192")
+
+
+def _run_bench(*extra):
     res = subprocess.run(
         [sys.executable, os.path.join(REPO, "bench.py"),
-         "--steps", "8", "--warmup", "2"],
+         "--steps", "8", "--warmup", "2", *extra],
         capture_output=True, text=True, timeout=600, cwd=REPO)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line expected"
-    out = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_full_adds_aux_metrics():
+    """--full carries the actor-side figures a plain run leaves out."""
+    out = _run_bench("--full")
+    assert out["steps"] == 8 and out["ms_per_step"] > 0
+    assert out["env_steps_per_sec_1actor"] > 0
+    assert out["env_steps_per_sec_vector64"] > 0
+    if out["config"]["device"] == "cuda":
+        assert out["env_steps_per_sec_gpu_rollout8192"] > 0
+    else:
+        assert out["env_steps_per_sec_gpu_rollout8192"] is None
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the learner state of the last timed step as
+    float32 .npy files; fixed seeds make two runs agree bit for bit."""
+    import numpy as np
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        _run_bench("--dump-outputs", d)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert {"actor.npy", "actor_target.npy", "critic.npy",
+            "critic_target.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a = np.load(os.path.join(dirs[0], n))
+        b = np.load(os.path.join(dirs[1], n))
+        assert a.dtype == np.float32 and a.size > 0
+        assert np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, b, err_msg=n)
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    # 10 optimizer steps moved the online nets off their targets
+    act = np.load(os.path.join(dirs[0], "actor.npy"))
+    tgt = np.load(os.path.join(dirs[0], "actor_target.npy"))
+    assert act.shape == tgt.shape and not np.array_equal(act, tgt)
+
+
+def test_bench_json_contract():
+    out = _run_bench()
+    # a plain run measures the headline only
+    assert not any(k in out for k in AUX_KEYS)
     # driver-contract fields (brief): metric/value/unit/n_gpus/steps/
     # warmup/ms_per_step/higher_is_better/scaling/vs_baseline/dtype/data/
     # config{model, global_batch, seq_len, parallelism}
