@@ -46,7 +46,9 @@ def categorical_projection(next_dist: torch.Tensor, rewards: torch.Tensor,
     z = torch.arange(K, device=device, dtype=dtype) * delta + v_min   # [K]
 
     tz = (r + gamma_n * (1.0 - d) * z).clamp_(v_min, v_max)          # [B, K]
-    b = (tz - v_min) / delta
+    # in float32 (v_max - v_min) / delta can round above K-1 (27.000002 at
+    # K=28 on [-300, 0]); uncapped, ceil(b) = K indexes past the support.
+    b = ((tz - v_min) / delta).clamp_(max=K - 1)
     l = b.floor().long()
     u = b.ceil().long()
     # equal-bin adjustment (see module docstring): exactly one bound moves.

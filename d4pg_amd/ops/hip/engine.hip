@@ -316,6 +316,21 @@ __global__ void k_fwd3(FwdJob j0, FwdJob j1, FwdJob j2, int njobs) {
         { fwd_one(j2, wg); return; }
 }
 
+// ---- C51 bin split shared by every projection copy --------------------------
+// Fractional bin position b of a clamped Tz and its two neighbour bins l < u.
+// In float32 (v_max - v_min) / delta can round ABOVE K-1 (e.g. 27.000002 at
+// K=28 on [-300, 0]); uncapped, ceil(b) = K indexes one float past the row.
+// Capping b at K-1 leaves every in-range value bit-identical.  Equal-bin
+// handling as in algo/projection.py (index-adjust so weights become (0,1)).
+__device__ __forceinline__ float c51_bins(float tz, float v_min, float delta,
+                                          int K, int& l, int& u) {
+    float b = fminf((tz - v_min) / delta, (float)(K - 1));
+    l = (int)floorf(b);
+    u = (int)ceilf(b);
+    if (l == u) { if (u > 0) l -= 1; else u += 1; }
+    return b;
+}
+
 // ---- C51 categorical projection (K3) ---------------------------------------
 // One wave per batch row; lane j < K owns atom j.  Mass split accumulated in
 // an LDS row via LDS atomics (no global scatter races).  Equal-bin handling
@@ -338,10 +353,8 @@ __global__ void k_project(const float* __restrict__ p_t,
         float z = v_min + lane * delta;
         float tz = r[row] + gamma_n * (1.f - d[row]) * z;
         tz = fminf(v_max, fmaxf(v_min, tz));
-        float b = (tz - v_min) / delta;
-        int l = (int)floorf(b);
-        int u = (int)ceilf(b);
-        if (l == u) { if (u > 0) l -= 1; else u += 1; }
+        int l, u;
+        float b = c51_bins(tz, v_min, delta, K, l, u);
         float p = p_t[(long)row * K + lane];
         atomicAdd(&mrow[l], p * ((float)u - b));
         atomicAdd(&mrow[u], p * (b - (float)l));
@@ -434,9 +447,8 @@ __global__ void k_project_ce(const float* __restrict__ p_t,
         float z = v_min + lane * delta;
         float tz = r[row] + gamma_n * (1.f - d[row]) * z;
         tz = fminf(v_max, fmaxf(v_min, tz));
-        float b = (tz - v_min) / delta;
-        int l = (int)floorf(b), u = (int)ceilf(b);
-        if (l == u) { if (u > 0) l -= 1; else u += 1; }
+        int l, u;
+        float b = c51_bins(tz, v_min, delta, K, l, u);
         float p = p_t[(long)row * K + lane];
         atomicAdd(&mrow[l], p * ((float)u - b));
         atomicAdd(&mrow[u], p * (b - (float)l));
@@ -685,9 +697,8 @@ k_critic_rowblock(RowBlockArgs g) {
             float z = g.v_min + lane * delta;
             float tz = rr + g.gamma_n * (1.f - dd) * z;
             tz = fminf(g.v_max, fmaxf(g.v_min, tz));
-            float bj = (tz - g.v_min) / delta;
-            int l = (int)floorf(bj), u = (int)ceilf(bj);
-            if (l == u) { if (u > 0) l -= 1; else u += 1; }
+            int l, u;
+            float bj = c51_bins(tz, g.v_min, delta, K, l, u);
             float p = L.r0[lane];
             atomicAdd(&L.r1[l], p * ((float)u - bj));
             atomicAdd(&L.r1[u], p * (bj - (float)l));
@@ -2063,7 +2074,11 @@ k_mfma_dw(const float* __restrict__ dz, const float* __restrict__ x1,
     int nch_seg = (nch_total + ksplit - 1) / ksplit;
     int ch0 = seg * nch_seg;
     int nch = min(nch_seg, nch_total - ch0);
-    if (nch <= 0) return;
+    // nch <= 0: an empty tail segment (ceil-split of a batch that is no
+    // power-of-two multiple of MT_K, e.g. B=640: 20 chunks over 16
+    // segments).  It must still publish ZERO partials — k_dw_reduce sums
+    // all ksplit segments, and `parts` holds stale data from earlier GEMMs.
+    // All loads below are row-guarded (b_base >= B), the chunk loop is empty.
     long b_base = (long)ch0 * MT_K;
     int tid = threadIdx.x, lane = tid & 63;
     f32x16 acc00 = {}, acc01 = {};
@@ -2915,9 +2930,8 @@ __device__ inline void p_project(const PStepArgs& g, float* lds) {
         float z = g.v_min + lane * delta;
         float tz = g.br[row] + g.gamma_n * (1.f - g.bd[row]) * z;
         tz = fminf(g.v_max, fmaxf(g.v_min, tz));
-        float b = (tz - g.v_min) / delta;
-        int l = (int)floorf(b), u = (int)ceilf(b);
-        if (l == u) { if (u > 0) l -= 1; else u += 1; }
+        int l, u;
+        float b = c51_bins(tz, g.v_min, delta, K, l, u);
         float p = g.p_t[(long)row * K + lane];
         atomicAdd(&mrow[l], p * ((float)u - b));
         atomicAdd(&mrow[u], p * (b - (float)l));
@@ -2945,9 +2959,8 @@ __device__ inline void p_project_ce(const PStepArgs& g, float* lds,
         float z = g.v_min + lane * delta;
         float tz = g.br[row] + g.gamma_n * (1.f - g.bd[row]) * z;
         tz = fminf(g.v_max, fmaxf(g.v_min, tz));
-        float b = (tz - g.v_min) / delta;
-        int l = (int)floorf(b), u = (int)ceilf(b);
-        if (l == u) { if (u > 0) l -= 1; else u += 1; }
+        int l, u;
+        float b = c51_bins(tz, g.v_min, delta, K, l, u);
         float p = g.p_t[(long)row * K + lane];
         atomicAdd(&mrow[l], p * ((float)u - b));
         atomicAdd(&mrow[u], p * (b - (float)l));
@@ -3293,9 +3306,8 @@ __device__ inline void p_proj_ce_rows(const PStepArgs& g, const float* pt_l,
         float z = g.v_min + lane * delta;
         float tz = g.br[row] + g.gamma_n * (1.f - g.bd[row]) * z;
         tz = fminf(g.v_max, fmaxf(g.v_min, tz));
-        float b = (tz - g.v_min) / delta;
-        int l = (int)floorf(b), u = (int)ceilf(b);
-        if (l == u) { if (u > 0) l -= 1; else u += 1; }
+        int l, u;
+        float b = c51_bins(tz, g.v_min, delta, K, l, u);
         float p = pt_l[rq * PXMAX + lane];
         atomicAdd(&mrow[l], p * ((float)u - b));
         atomicAdd(&mrow[u], p * (b - (float)l));
@@ -4005,7 +4017,8 @@ public:
         az3 = carve<float>((long)B * H, off);
         // split-K dW disjoint partials (wide path only): max over layers
         // of ksplit * (weights + bias); the ksplit formula mirrors
-        // launch_bwd's and guarantees every segment is non-empty
+        // launch_bwd's.  Segments past the last batch chunk are empty when
+        // B is no power-of-two multiple of MT_K; k_mfma_dw zero-fills them
         long dwp = 0;
         if (B >= 512) {
             auto dw_need = [&](int in_n, int out) {

@@ -247,6 +247,9 @@ static py::dict counters(int64_t h) {
     d["beta_t"] = c.beta_t;
     d["adam_t_actor"] = c.adam_t_actor;
     d["adam_t_critic"] = c.adam_t_critic;
+    // steps completed, like the adam counters: the NEXT step draws its
+    // probes with philox epoch rng_epoch + 1
+    d["rng_epoch"] = c.rng_epoch;
     d["size"] = c.size;
     d["pos"] = c.pos;
     d["max_priority"] = c.max_priority;

@@ -1,0 +1,188 @@
+"""Plain numpy oracles for the fused engine's PER sampling and C51
+projection (shared by the CPU and GPU tests; not a conftest).
+
+Everything here is written for clarity, not speed: python loops, float64
+mass arithmetic.  Where the engine's result depends on a float32 rounding
+(the philox -> (0,1] map, the beta schedule, the projection's bin position)
+that rounding is reproduced so the *discrete* choices (leaf, bin) are the
+engine's own and only the continuous arithmetic is higher precision.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+_M0, _M1 = 0xD2511F53, 0xCD9E8D57
+_W0, _W1 = 0x9E3779B9, 0xBB67AE85
+_MASK = 0xFFFFFFFF
+
+
+def philox4x32_10_raw(ctr, key):
+    """philox4x32-10 on a 4-word counter and 2-word key (Salmon et al.,
+    'Parallel random numbers: as easy as 1, 2, 3', SC'11)."""
+    c0, c1, c2, c3 = (int(x) & _MASK for x in ctr)
+    k0, k1 = (int(x) & _MASK for x in key)
+    for _ in range(10):
+        p0, p1 = _M0 * c0, _M1 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0, p1 & _MASK,
+                          (p0 >> 32) ^ c3 ^ k1, p0 & _MASK)
+        k0, k1 = (k0 + _W0) & _MASK, (k1 + _W1) & _MASK
+    return c0, c1, c2, c3
+
+
+def philox4x32_10(seed, ctr_hi, ctr_lo):
+    """The engine's calling convention: 64-bit seed -> key, 64-bit ctr_lo ->
+    counter words 0,1 and 64-bit ctr_hi -> counter words 2,3."""
+    seed, ctr_hi, ctr_lo = int(seed), int(ctr_hi), int(ctr_lo)
+    return philox4x32_10_raw(
+        (ctr_lo, ctr_lo >> 32, ctr_hi, ctr_hi >> 32), (seed, seed >> 32))
+
+
+def u01(x):
+    """uint32 -> (0, 1] exactly as the kernel rounds it: cast to float32,
+    add 1, multiply by 2^-32 (as the float32 literal), all in float32."""
+    f = np.float32(np.uint32(int(x) & _MASK))
+    return np.float32(np.float32(f + np.float32(1.0))
+                      * np.float32(2.3283064e-10))
+
+
+def probe_mass(seed, epoch, probe, total):
+    """The sum-tree mass probe `probe` of step-epoch `epoch` descends with."""
+    return float(u01(philox4x32_10(seed, epoch, probe)[0])) * float(total)
+
+
+def build_trees(leaf_pri, tree_cap):
+    """Binary-heap sum and min trees (node n has children 2n, 2n+1; leaves at
+    [tree_cap, 2*tree_cap)) over `leaf_pri`, built bottom-up in float64 so
+    every parent is bitwise the sum / min of its two children.  Unoccupied
+    leaves hold what a fresh engine holds: 0 in the sum tree, +inf in the
+    min tree (slot 0 is unused and keeps the same fill)."""
+    leaf_pri = np.asarray(leaf_pri, np.float64)
+    n = leaf_pri.shape[0]
+    assert n <= tree_cap and tree_cap & (tree_cap - 1) == 0
+    st = np.zeros(2 * tree_cap, np.float64)
+    mt = np.full(2 * tree_cap, np.inf, np.float64)
+    st[tree_cap:tree_cap + n] = leaf_pri
+    mt[tree_cap:tree_cap + n] = leaf_pri
+    for node in range(tree_cap - 1, 0, -1):
+        st[node] = st[2 * node] + st[2 * node + 1]
+        mt[node] = min(mt[2 * node], mt[2 * node + 1])
+    return st, mt
+
+
+def descend(sum_tree, tree_cap, mass, size):
+    """The specification of a PER draw: plain binary descent.  Go left if
+    mass <= left child, else subtract it and go right; a leaf past the
+    occupied range (fp round-off at the top) snaps to size-1."""
+    node = 1
+    mass = float(mass)
+    while node < tree_cap:
+        left = float(sum_tree[2 * node])
+        if mass <= left:
+            node = 2 * node
+        else:
+            mass -= left
+            node = 2 * node + 1
+    idx = node - tree_cap
+    return size - 1 if idx >= size else idx
+
+
+def per_beta(beta0, beta_iters, beta_t):
+    """float32 beta schedule as the sampling kernels compute it."""
+    frac = min(np.float32(np.float64(beta_t)
+                          / np.float64(np.float32(beta_iters))),
+               np.float32(1.0))
+    return np.float32(np.float32(beta0)
+                      + np.float32(frac * np.float32(np.float32(1.0)
+                                                     - np.float32(beta0))))
+
+
+def is_weights(sum_tree, min_tree, idx, size, beta0, beta_iters, beta_t):
+    """w_i = ((p_i/total) * N)^-beta / max_w, max_w = ((p_min/total)*N)^-beta
+    (float64 throughout; beta is the float32 schedule value)."""
+    tree_cap = len(sum_tree) // 2
+    beta = float(per_beta(beta0, beta_iters, beta_t))
+    total = float(sum_tree[1])
+    idx = np.asarray(idx, np.int64)
+    p = np.asarray(sum_tree, np.float64)[tree_cap + idx] / total
+    p_min = float(min_tree[1]) / total
+    max_w = (p_min * size) ** (-beta)
+    return (p * size) ** (-beta) / max_w
+
+
+def project64(p, r, d, v_min, v_max, gamma_n):
+    """C51 projection, per row and per atom, masses in float64.
+
+    The bin position b of each shifted atom is taken from float32 arithmetic
+    (the values the kernel sees), capped at K-1, and only then split in
+    float64 — so the bin choice is the kernel's and the oracle adds no
+    bin-flip noise of its own.  Equal-bin rule: when b is integral, all of
+    the atom's mass goes to bin b."""
+    f = np.float32
+    p = np.asarray(p, np.float64)
+    r = np.asarray(r, np.float32).ravel()
+    d = np.asarray(d, np.float32).ravel()
+    B, K = p.shape
+    v_min, v_max, gamma_n = f(v_min), f(v_max), f(gamma_n)
+    delta = f(f(v_max - v_min) / f(K - 1))
+    m = np.zeros((B, K), np.float64)
+    for i in range(B):
+        g = f(gamma_n * f(f(1.0) - d[i]))
+        for j in range(K):
+            z = f(v_min + f(f(j) * delta))
+            tz = f(r[i] + f(g * z))
+            tz = min(v_max, max(v_min, tz))
+            b = min(f(f(tz - v_min) / delta), f(K - 1))
+            lo, hi = int(np.floor(b)), int(np.ceil(b))
+            if lo == hi:
+                m[i, lo] += p[i, j]
+            else:
+                m[i, lo] += p[i, j] * (hi - float(b))
+                m[i, hi] += p[i, j] * (float(b) - lo)
+    return m
+
+
+# ---------------------------------------------------------------------------
+# edge-case reward/done rows for the projection tests
+# ---------------------------------------------------------------------------
+
+N_CATEGORIES = 8
+
+
+def edge_rows(n, K, v_min, v_max, seed=0):
+    """n (reward, done) rows whose category is `index % 8`:
+      0  r far above v_max, done      1  r far above v_max, not done
+      2  r far below v_min            3  done, r = float32(v_min + j*delta)
+      4  done, r = v_min exactly         for j cycling over 0, 1, K//2, K-1
+      5  done, r = v_max exactly      6  interior, not done
+      7  interior, done
+    """
+    f = np.float32
+    rng = np.random.default_rng(seed)
+    delta = f(f(f(v_max) - f(v_min)) / f(K - 1))
+    span = float(v_max) - float(v_min)
+    js = [0, 1, K // 2, K - 1]
+    r = np.zeros(n, np.float32)
+    d = np.zeros(n, np.float32)
+    for i in range(n):
+        c = i % N_CATEGORIES
+        if c == 0:
+            r[i], d[i] = v_max + 10.0 * span, 1.0
+        elif c == 1:
+            r[i], d[i] = v_max + 10.0 * span, 0.0
+        elif c == 2:
+            r[i], d[i] = v_min - 10.0 * span, 0.0
+        elif c == 3:
+            j = js[(i // N_CATEGORIES) % 4]
+            r[i], d[i] = f(f(v_min) + f(f(j) * delta)), 1.0
+        elif c == 4:
+            r[i], d[i] = v_min, 1.0
+        elif c == 5:
+            r[i], d[i] = v_max, 1.0
+        elif c == 6:
+            r[i], d[i] = rng.uniform(0.1 * span, 0.3 * span), 0.0
+            r[i] = f(r[i] - f(0.35 * span))    # straddles some clamping
+        else:
+            r[i], d[i] = rng.uniform(v_min + 0.05 * span,
+                                     v_max - 0.05 * span), 1.0
+    return r, d
