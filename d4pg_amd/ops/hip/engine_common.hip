@@ -1,0 +1,130 @@
+// Common types (layer geometry, config, device counters), the philox RNG and
+// the small device helpers every path shares.  Used by all other parts.
+//
+// Numerics: fp32 end-to-end, matching the reference's CPU fp32; per-thread
+// dot products accumulate in ascending-k order so every path agrees with
+// the eager torch oracle within fp32 tolerance.
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <cstdlib>
+#include <cmath>
+#include <vector>
+#include <stdexcept>
+
+#define HIP_CHECK(cmd) do { \
+    hipError_t e_ = (cmd); \
+    if (e_ != hipSuccess) { \
+        char buf[256]; \
+        snprintf(buf, sizeof(buf), "HIP error %s at %s:%d", \
+                 hipGetErrorString(e_), __FILE__, __LINE__); \
+        throw std::runtime_error(buf); \
+    } \
+} while (0)
+
+namespace d4pg {
+
+// ---------------------------------------------------------------------------
+// philox4x32-10 counter-based RNG (device)
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t mulhi32(uint32_t a, uint32_t b) {
+    return (uint32_t)(((uint64_t)a * b) >> 32);
+}
+
+struct Philox4 { uint32_t v[4]; };
+
+__device__ inline Philox4 philox4(uint64_t seed, uint64_t ctr_hi,
+                                  uint64_t ctr_lo) {
+    uint32_t c0 = (uint32_t)ctr_lo, c1 = (uint32_t)(ctr_lo >> 32);
+    uint32_t c2 = (uint32_t)ctr_hi, c3 = (uint32_t)(ctr_hi >> 32);
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+    const uint32_t W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        uint32_t hi0 = mulhi32(M0, c0), lo0 = M0 * c0;
+        uint32_t hi1 = mulhi32(M1, c2), lo1 = M1 * c2;
+        uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1;
+        uint32_t n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += W0; k1 += W1;
+    }
+    return {c0, c1, c2, c3};
+}
+
+__device__ inline float u01(uint32_t x) {           // (0,1]
+    return ((float)x + 1.0f) * 2.3283064e-10f;
+}
+
+// ---------------------------------------------------------------------------
+// Engine state blocks
+// ---------------------------------------------------------------------------
+
+// One linear layer's geometry inside a parameter slab.
+struct LayerDesc {
+    int in1, in2, out;       // in2 > 0 => concat second input
+    long w_off, b_off;       // offsets into the net's slab (floats)
+};
+
+enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_SOFTMAX = 3 };
+
+struct EngineCfg {
+    int obs, act, hidden, atoms, batch;
+    long capacity;             // replay capacity (will be rounded to pow2 tree)
+    float v_min, v_max, gamma_n, tau, lr_actor, lr_critic;
+    float per_alpha, per_beta0, per_eps;
+    long per_beta_iters;
+    uint64_t seed;
+    int is_weighting;          // apply IS weights to the CE loss
+};
+
+// device-side counters (one small block)
+struct Counters {
+    long long beta_t;          // PER beta schedule position (stateful)
+    long long adam_t_actor;
+    long long adam_t_critic;
+    long long rng_epoch;       // bumped per step for fresh philox streams
+    long long size;            // replay occupancy
+    long long pos;             // replay ring position
+    float max_priority;
+    float loss_critic;         // per-step scalars (overwritten each step)
+    float loss_actor;
+};
+
+// max fan-in a fwd workgroup stages (hidden(1024) + act margin)
+#define FWD_XMAX 1032
+
+// ---- C51 bin split shared by every projection copy --------------------------
+// Fractional bin position b of a clamped Tz and its two neighbour bins l < u.
+// In float32 (v_max - v_min) / delta can round ABOVE K-1 (e.g. 27.000002 at
+// K=28 on [-300, 0]); uncapped, ceil(b) = K indexes one float past the row.
+// Capping b at K-1 leaves every in-range value bit-identical.  Equal-bin
+// handling as in algo/projection.py (index-adjust so weights become (0,1)).
+__device__ __forceinline__ float c51_bins(float tz, float v_min, float delta,
+                                          int K, int& l, int& u) {
+    float b = fminf((tz - v_min) / delta, (float)(K - 1));
+    l = (int)floorf(b);
+    u = (int)ceilf(b);
+    if (l == u) { if (u > 0) l -= 1; else u += 1; }
+    return b;
+}
+
+__device__ inline float act_mask(int act, float h) {
+    if (act == ACT_RELU) return h > 0.f ? 1.f : 0.f;
+    if (act == ACT_TANH) return 1.f - h * h;
+    return 1.f;
+}
+
+// Layer pointer bundle for a net slab.
+struct NetPtrs { const float *w1, *b1, *w2, *b2, *w3, *b3, *w4, *b4; };
+
+__device__ inline NetPtrs net_ptrs(const float* slab, const LayerDesc* l) {
+    return {slab + l[0].w_off, slab + l[0].b_off,
+            slab + l[1].w_off, slab + l[1].b_off,
+            slab + l[2].w_off, slab + l[2].b_off,
+            slab + l[3].w_off, slab + l[3].b_off};
+}
+
+}  // namespace d4pg

@@ -1,0 +1,174 @@
+// Device rollout kernels: M vectorized Pendulum envs, exploration noise and the
+// n-step fold, writing transitions straight into the on-HBM replay.  Used by
+// Engine::rollout_* (GPU actor ranks); the policy forward between ticks is
+// k_fwd below 512 envs and k_mfma_fwd from 512 up.
+
+namespace d4pg {
+
+// ===========================================================================
+// GPU-resident actor rollout: M vectorized Pendulum envs + exploration
+// noise (K11) + n-step fold (K15) entirely on device, transitions written
+// straight into the on-HBM replay ring.  Re-expresses the reference's
+// per-env-step actor loop (main.py:142-152 + random_process.py:4-45) and
+// the host twins VectorPendulum / VecNStep (d4pg_amd/envs/vector.py), which
+// serve as the parity oracles.
+//
+// Per tick: [fwd chain obs->act over M rows] then ONE k_roll_tick kernel
+// (noise + dynamics + ring write + n-step emit).  Tree leaves are written
+// at emit; internal nodes are rebuilt ONCE per episode by the full
+// per-level sweep (k_tree_build_level — ~2M f64 nodes, bandwidth-cheap),
+// which beats per-tick path repair by orders of magnitude.  The whole
+// episode is one hipGraph; per-episode variability (philox epoch, replay
+// base position) lives in device memory so graph replays stay fresh.
+// ===========================================================================
+
+__device__ inline float d4pg_angle_norm(float x) {
+    const float PI = 3.14159265358979323846f;
+    float y = fmodf(x + PI, 2.0f * PI);
+    if (y < 0.0f) y += 2.0f * PI;
+    return y - PI;
+}
+
+// standard normal via Box-Muller on two philox lanes
+__device__ inline float n01(uint32_t a, uint32_t b) {
+    float u1 = u01(a), u2 = u01(b);
+    u1 = fmaxf(u1, 1e-12f);
+    return sqrtf(-2.0f * logf(u1)) *
+           cosf(6.283185307179586f * u2);
+}
+
+struct RollArgs {
+    int M, O, A, n, horizon;
+    float gamma, eps, ou_theta, ou_sigma, ou_mu, ou_dt;
+    int noise_kind;                    // 0 = gaussian, 1 = OU
+    uint64_t seed;
+    float per_alpha;
+    // env + noise state
+    float *th, *thdot, *obs, *act, *ou_x;
+    // n-step rings [n][M][*]
+    float *s_ring, *a_ring, *r_ring;
+    // per-episode device state: [0] philox epoch, [1] replay base pos
+    long long* ep_state;
+    // replay
+    float *rs, *ra, *rr, *rs2, *rd;
+    double *sum_tree, *min_tree;
+    long tree_cap, capacity;
+    Counters* cnt;
+};
+
+// episode prologue: bump the philox epoch, latch the replay write base
+__global__ void k_roll_begin(RollArgs a) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        a.ep_state[0] += 1;
+        a.ep_state[1] = a.cnt->pos;
+    }
+}
+
+// reset all M envs (uniform th in [-pi,pi], thdot in [-1,1] — Pendulum-v1
+// reset distribution) + OU state to mu, and emit the first observation
+__global__ void k_roll_reset(RollArgs a) {
+    long long ep = a.ep_state[0];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.M;
+         i += gridDim.x * blockDim.x) {
+        Philox4 r = philox4(a.seed ^ 0xD011Eull, ((uint64_t)ep << 20) | 1u,
+                            (uint64_t)i);
+        float th = (2.0f * u01(r.v[0]) - 1.0f) * 3.14159265358979f;
+        float td = 2.0f * u01(r.v[1]) - 1.0f;
+        a.th[i] = th;
+        a.thdot[i] = td;
+        a.obs[i * 3 + 0] = cosf(th);
+        a.obs[i * 3 + 1] = sinf(th);
+        a.obs[i * 3 + 2] = td;
+        for (int k = 0; k < a.A; ++k) a.ou_x[i * a.A + k] = a.ou_mu;
+    }
+}
+
+// one synchronized tick for all M envs: noise -> clip -> dynamics ->
+// n-step ring write -> (optional) matured-transition emit into the replay.
+// slot/emit_k/done are per-tick constants baked into the episode graph.
+__global__ void k_roll_tick(RollArgs a, int tick, int slot, int emit_k,
+                            int done) {
+    long long ep = a.ep_state[0];
+    long long base = a.ep_state[1];
+    double pa = pow((double)a.cnt->max_priority, (double)a.per_alpha);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.M;
+         i += gridDim.x * blockDim.x) {
+        // --- exploration noise (K11): per-env per-tick philox stream ---
+        float u_n = a.act[i * a.A];        // policy output, tanh in (-1,1)
+        if (a.noise_kind == 0 && a.eps != 0.0f) {
+            Philox4 r = philox4(a.seed ^ 0x2F01Eull,
+                                ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
+                                (uint64_t)i);
+            u_n += a.eps * n01(r.v[0], r.v[1]);
+        } else if (a.noise_kind == 1) {
+            Philox4 r = philox4(a.seed ^ 0x2F01Eull,
+                                ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
+                                (uint64_t)i);
+            float x = a.ou_x[i * a.A];
+            x += a.ou_theta * (a.ou_mu - x) * a.ou_dt
+                 + a.ou_sigma * sqrtf(a.ou_dt) * n01(r.v[0], r.v[1]);
+            a.ou_x[i * a.A] = x;
+            u_n += a.eps * x;
+        }
+        u_n = fminf(fmaxf(u_n, -1.0f), 1.0f);
+
+        // --- n-step ring: store s_t, a_t BEFORE stepping ---
+        a.s_ring[(slot * a.M + i) * 3 + 0] = a.obs[i * 3 + 0];
+        a.s_ring[(slot * a.M + i) * 3 + 1] = a.obs[i * 3 + 1];
+        a.s_ring[(slot * a.M + i) * 3 + 2] = a.obs[i * 3 + 2];
+        a.a_ring[slot * a.M + i] = u_n;
+
+        // --- Pendulum dynamics (VectorPendulum.step parity) ---
+        const float max_torque = 2.0f, max_speed = 8.0f, dt = 0.05f,
+                    g = 10.0f;
+        float th = a.th[i], td = a.thdot[i];
+        float u = u_n * max_torque;
+        float an = d4pg_angle_norm(th);
+        float cost = an * an + 0.1f * td * td + 0.001f * u * u;
+        float newtd = td + (1.5f * g * sinf(th) + 3.0f * u) * dt;
+        newtd = fminf(fmaxf(newtd, -max_speed), max_speed);
+        th = th + newtd * dt;
+        a.th[i] = th;
+        a.thdot[i] = newtd;
+        a.r_ring[slot * a.M + i] = -cost;
+        float o0 = cosf(th), o1 = sinf(th), o2 = newtd;
+        a.obs[i * 3 + 0] = o0;
+        a.obs[i * 3 + 1] = o1;
+        a.obs[i * 3 + 2] = o2;
+
+        // --- matured n-step emit (VecNStep parity): transition
+        // (s_{t-n+1}, a_{t-n+1}, sum gamma^k r, s_{t+1}, done) ---
+        if (emit_k >= 0) {
+            int start = (slot + 1) % a.n;       // oldest ring entry
+            float R = 0.0f, gk = 1.0f;
+            for (int k = 0; k < a.n; ++k) {
+                R += gk * a.r_ring[((start + k) % a.n) * a.M + i];
+                gk *= a.gamma;
+            }
+            long dst = (base + (long)emit_k * a.M + i) % a.capacity;
+            a.rs[dst * 3 + 0] = a.s_ring[(start * a.M + i) * 3 + 0];
+            a.rs[dst * 3 + 1] = a.s_ring[(start * a.M + i) * 3 + 1];
+            a.rs[dst * 3 + 2] = a.s_ring[(start * a.M + i) * 3 + 2];
+            a.ra[dst] = a.a_ring[start * a.M + i];
+            a.rr[dst] = R;
+            a.rs2[dst * 3 + 0] = o0;
+            a.rs2[dst * 3 + 1] = o1;
+            a.rs2[dst * 3 + 2] = o2;
+            a.rd[dst] = (float)done;
+            a.sum_tree[a.tree_cap + dst] = pa;
+            a.min_tree[a.tree_cap + dst] = pa;
+        }
+    }
+}
+
+// episode epilogue: advance the replay counters by the emitted block
+__global__ void k_roll_end(RollArgs a, long emitted) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        long long base = a.ep_state[1];
+        a.cnt->pos = (base + emitted) % a.capacity;
+        long long sz = a.cnt->size + emitted;
+        a.cnt->size = sz > a.capacity ? a.capacity : sz;
+    }
+}
+
+}  // namespace d4pg

@@ -49,7 +49,7 @@ static py::dict info(int64_t h) {
     d["n_params_actor"] = e.anet.n_params;
     d["n_params_critic"] = e.cnet.n_params;
     d["tree_cap"] = e.tree_cap;
-    d["persistent"] = e.use_persistent();
+    d["persistent"] = e.step_path() == Engine::PATH_PERSISTENT;
     d["seed"] = (int64_t)e.cfg.seed;
     py::list al, cl;
     for (int i = 0; i < 4; ++i) {
@@ -309,7 +309,7 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
               H = e.cfg.hidden, K = e.cfg.atoms;
     // the persistent path double-buffers bs by step parity; resolve the
     // buffer the LAST completed step actually used
-    if (name == "bs" && e.use_persistent()) {
+    if (name == "bs" && e.step_path() == Engine::PATH_PERSISTENT) {
         Counters c = e.read_counters();
         if (c.beta_t > 0 && ((c.beta_t - 1) & 1))
             name = "bs_b";

@@ -48,7 +48,7 @@ __global__ void k_mfma_peak(float* out, int iters) {
     out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
 
-// MFMA with operands streamed from LDS exactly like mfma_pipeline's ks
+// MFMA with operands streamed from LDS exactly like mfma_pipeline_w's ks
 // loop (3 ds_read_b32 per 2 MFMAs, padded rows).  PIPE=0: naive reads
 // right before use (what the compiler makes of it); PIPE=1: 2-stage
 // manual operand prefetch (read ks+2's operands before ks's MFMAs issue).

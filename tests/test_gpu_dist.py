@@ -214,7 +214,7 @@ def test_bench_multirank_gloo_end_to_end():
 
 def test_split_step_matches_full_step_wide_mfma_path():
     """Split-step (DP insertion points) parity on the WIDE path too —
-    B >= 512 takes the per-layer MFMA kernels, a different code path from
+    B > 512 takes the per-layer MFMA kernels, a different code path from
     the row-block form covered above."""
     from d4pg_amd.models import actor, critic
     from d4pg_amd.ops import FusedEngine

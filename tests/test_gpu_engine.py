@@ -242,6 +242,26 @@ def test_actor_forward_matches_module():
     np.testing.assert_allclose(y.numpy(), ref.numpy(), atol=2e-5)
 
 
+def test_actor_forward_512_rows_at_batch_512():
+    """B = 512 is where the two thresholds part: a train step is still
+    row-block there, while a forward over 512 rows already takes the MFMA
+    kernels (split-K tanh head with its partials in the dW scratch)."""
+    from d4pg_amd.models import actor
+    from d4pg_amd.ops import FusedEngine, pack_net
+    eng = FusedEngine(obs_dim=O, act_dim=A, hidden=64, n_atoms=K, batch=512,
+                      capacity=1024, v_min=-300.0, v_max=0.0,
+                      gamma_n=GAMMA_N, tau=TAU, lr_actor=LR, lr_critic=LR,
+                      seed=4)
+    torch.manual_seed(5)
+    a = actor(O, A, hidden=64)
+    eng.load_slab("actor", pack_net(a))
+    x = torch.randn(512, O)
+    y = eng.actor_forward(x)
+    with torch.no_grad():
+        ref = a(x)
+    np.testing.assert_allclose(y.numpy(), ref.numpy(), atol=2e-5)
+
+
 def test_synth_fill_and_throughput_sanity():
     """synth_fill populates a consistent tree and the engine sustains
     hundreds of steps without numerical blowup."""

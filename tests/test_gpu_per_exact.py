@@ -220,7 +220,7 @@ def test_is_weighting_scales_loss_and_gradient(B, g_atol):
     assert np.abs(w["g_critic"] - u["g_critic"]).max() > 10 * g_atol
 
 
-# B=640 repairs the tree with k_per_leaves + k_per_level4 (B >= 512)
+# B=640 repairs the tree with k_per_leaves + k_per_level4 (B > 512)
 @pytest.mark.parametrize("B", [64, 300, 640])
 def test_tree_invariant_after_writeback(B):
     eng = _engine(B, 1024)

@@ -72,8 +72,9 @@ def test_engine_resume_bitwise():
 
 
 def test_engine_resume_wide_batch_graph_path():
-    """the wide/graph path (B >= 512, hipGraph
-    replay) bakes the philox seed into captured kernel ARGUMENTS, so a
+    """the hipGraph-replayed paths (here B = 512, the
+    row-block kernels; the wide MFMA path, B > 512, replays the same way)
+    bake the philox seed into captured kernel ARGUMENTS, so a
     restored seed must invalidate the graph — otherwise a resumed run
     silently keeps the stale seed.  Verifies the post-restore trajectory
     matches the original bitwise THROUGH graph-replayed steps."""

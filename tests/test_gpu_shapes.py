@@ -1,7 +1,7 @@
 """Engine parity at awkward shapes: dims that don't divide the tile sizes
 (64-col chunks, 4-row tiles, wave-wide softmax) and batches that select
 each execution path — persistent (B<=256), row-block (256<B<=512), and
-MFMA (B>=512) — all against the eager fp32 oracle."""
+MFMA (B>512) — all against the eager fp32 oracle."""
 
 import copy
 

@@ -1,4 +1,4 @@
-"""GPU parity for the wide-batch (MFMA) engine paths: B >= 512 routes the
+"""GPU parity for the wide-batch (MFMA) engine paths: B > 512 routes the
 layer GEMMs through the matrix-core kernels (k_mfma_fwd/dx/dw, split-K,
 per-level PER repair) — replicate one full step in eager fp32 torch on the
 identical sampled batch and compare every stage."""
