@@ -23,6 +23,7 @@
 // capture and replay, replay ingestion, parameter I/O, the rollout driver.
 
 #include "engine_common.hip"
+#include "engine_rowmath.hip"
 #include "engine_replay.hip"
 #include "engine_layer.hip"
 #include "engine_rowblock.hip"
@@ -71,35 +72,17 @@ class Engine {
 public:
     EngineCfg cfg;
     Net anet, cnet;
-    long tree_cap;
     hipStream_t stream;
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int graph_steps = 0;
 
-    // device buffers
-    float *p_actor, *p_actor_t, *p_critic, *p_critic_t;
-    float *g_actor, *g_critic;
-    float *m_actor, *v_actor, *m_critic, *v_critic;
-    float *rs, *ra, *rr, *rs2, *rd;                 // replay SoA
-    double *sum_tree, *min_tree;
-    Counters* cnt;
-    // batch + activations workspace
-    float *bs, *bs_b, *ba, *br, *bs2, *bd, *bw, *pri;
-    long *bidx;
-    float *at_h1, *at_h2, *at_h3, *a2;              // actor_target path
-    float *ct_h1, *ct_h2, *ct_h3, *p_t, *m_proj;    // critic_target path
-    float *c_h1, *c_h2, *c_h3, *q;                  // critic path
-    float *dlog, *d3, *d2, *d1, *da;                // critic backward deltas
-    float *pa_h1, *pa_h2, *pa_h3, *a_out;           // actor (policy) path
-    float *pc_h1, *pc_h2, *pc_h3, *pq;              // critic(s, actor(s))
-    float *pd3, *pd2, *pdh1, *pda, *adz;            // policy backward deltas
-    float *az1, *az2, *az3;                         // actor per-layer dz rows
+    // step geometry + every workspace pointer, as the kernels take them
+    // (scalars filled by the constructor, pointers carved by layout())
+    StepArgs ws{};
     float *ing_s, *ing_a, *ing_r, *ing_s2, *ing_d;  // ingestion staging
     float* dw_parts;                                // split-K dW partials
     int ing_cap;
-    unsigned long long* gbar;                       // persistent grid barrier
-    unsigned long long* tstamp;                     // phase timing probe
 
     Engine(const EngineCfg& c) : cfg(c) {
         if (c.hidden + c.act > FWD_XMAX || c.obs > FWD_XMAX)
@@ -108,7 +91,20 @@ public:
             throw std::runtime_error("n_atoms > 64 (softmax is wave-wide)");
         anet = make_actor_net(c.obs, c.act, c.hidden);
         cnet = make_critic_net(c.obs, c.act, c.hidden, c.atoms);
-        tree_cap = next_pow2(c.capacity);
+        ws.B = c.batch; ws.O = c.obs; ws.A = c.act; ws.H = c.hidden;
+        ws.K = c.atoms;
+        ws.v_min = c.v_min; ws.v_max = c.v_max; ws.gamma_n = c.gamma_n;
+        ws.per_eps = c.per_eps; ws.tau = c.tau;
+        ws.lr_actor = c.lr_actor; ws.lr_critic = c.lr_critic;
+        ws.per_alpha = c.per_alpha; ws.per_beta0 = c.per_beta0;
+        ws.per_beta_iters = (float)c.per_beta_iters;
+        ws.is_weighting = c.is_weighting;
+        ws.seed = c.seed; ws.tree_cap = next_pow2(c.capacity);
+        ws.n_actor = anet.n_params; ws.n_critic = cnet.n_params;
+        for (int i = 0; i < 4; ++i) {
+            ws.al[i] = anet.l[i];
+            ws.cl[i] = cnet.l[i];
+        }
         HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         // co-residency gate for the persistent path: all PNWG workgroups
         // must fit on the device at once or the software grid barrier
@@ -133,7 +129,7 @@ public:
     // must be considered corrupt after it
     void check_bar_error() {
         unsigned long long e = 0;
-        HIP_CHECK(hipMemcpy(&e, gbar + 176, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&e, ws.gbar + 176, 8, hipMemcpyDeviceToHost));
         if (e)
             throw std::runtime_error(
                 "persistent grid barrier timed out (desynchronized "
@@ -169,59 +165,63 @@ public:
         const long pa = anet.n_params, pc = cnet.n_params;
         ing_cap = 65536;
         long off = 0;
-        p_actor = carve<float>(pa, off);  p_actor_t = carve<float>(pa, off);
-        g_actor = carve<float>(pa, off);
-        p_critic = carve<float>(pc, off); p_critic_t = carve<float>(pc, off);
-        g_critic = carve<float>(pc, off);
-        m_actor = carve<float>(pa, off);  v_actor = carve<float>(pa, off);
-        m_critic = carve<float>(pc, off); v_critic = carve<float>(pc, off);
-        rs = carve<float>(C * O, off); ra = carve<float>(C * A, off);
-        rr = carve<float>(C, off); rs2 = carve<float>(C * O, off);
-        rd = carve<float>(C, off);
-        sum_tree = carve<double>(2 * tree_cap, off);
-        min_tree = carve<double>(2 * tree_cap, off);
-        cnt = carve<Counters>(1, off);
-        bs = carve<float>((long)B * O, off);
-        bs_b = carve<float>((long)B * O, off);
-        ba = carve<float>((long)B * A, off);
-        br = carve<float>(B, off); bs2 = carve<float>((long)B * O, off);
-        bd = carve<float>(B, off); bw = carve<float>(B, off);
-        pri = carve<float>(B, off);
-        bidx = carve<long>(B, off);
-        at_h1 = carve<float>((long)B * H, off);
-        at_h2 = carve<float>((long)B * H, off);
-        at_h3 = carve<float>((long)B * H, off);
-        a2 = carve<float>((long)B * A, off);
-        ct_h1 = carve<float>((long)B * H, off);
-        ct_h2 = carve<float>((long)B * H, off);
-        ct_h3 = carve<float>((long)B * H, off);
-        p_t = carve<float>((long)B * K, off);
-        m_proj = carve<float>((long)B * K, off);
-        c_h1 = carve<float>((long)B * H, off);
-        c_h2 = carve<float>((long)B * H, off);
-        c_h3 = carve<float>((long)B * H, off);
-        q = carve<float>((long)B * K, off);
-        dlog = carve<float>((long)B * K, off);
-        d3 = carve<float>((long)B * H, off);
-        d2 = carve<float>((long)B * H, off);
-        d1 = carve<float>((long)B * H, off);
-        da = carve<float>((long)B * A, off);
-        pa_h1 = carve<float>((long)B * H, off);
-        pa_h2 = carve<float>((long)B * H, off);
-        pa_h3 = carve<float>((long)B * H, off);
-        a_out = carve<float>((long)B * A, off);
-        pc_h1 = carve<float>((long)B * H, off);
-        pc_h2 = carve<float>((long)B * H, off);
-        pc_h3 = carve<float>((long)B * H, off);
-        pq = carve<float>((long)B * K, off);
-        pd3 = carve<float>((long)B * K, off);
-        pd2 = carve<float>((long)B * H, off);
-        pdh1 = carve<float>((long)B * H, off);
-        pda = carve<float>((long)B * A, off);
-        adz = carve<float>((long)B * A, off);
-        az1 = carve<float>((long)B * H, off);
-        az2 = carve<float>((long)B * H, off);
-        az3 = carve<float>((long)B * H, off);
+        ws.p_actor = carve<float>(pa, off);
+        ws.p_actor_t = carve<float>(pa, off);
+        ws.g_actor = carve<float>(pa, off);
+        ws.p_critic = carve<float>(pc, off);
+        ws.p_critic_t = carve<float>(pc, off);
+        ws.g_critic = carve<float>(pc, off);
+        ws.m_actor = carve<float>(pa, off);
+        ws.v_actor = carve<float>(pa, off);
+        ws.m_critic = carve<float>(pc, off);
+        ws.v_critic = carve<float>(pc, off);
+        ws.rs = carve<float>(C * O, off); ws.ra = carve<float>(C * A, off);
+        ws.rr = carve<float>(C, off); ws.rs2 = carve<float>(C * O, off);
+        ws.rd = carve<float>(C, off);
+        ws.sum_tree = carve<double>(2 * ws.tree_cap, off);
+        ws.min_tree = carve<double>(2 * ws.tree_cap, off);
+        ws.cnt = carve<Counters>(1, off);
+        ws.bs = carve<float>((long)B * O, off);
+        ws.bs_b = carve<float>((long)B * O, off);
+        ws.ba = carve<float>((long)B * A, off);
+        ws.br = carve<float>(B, off); ws.bs2 = carve<float>((long)B * O, off);
+        ws.bd = carve<float>(B, off); ws.bw = carve<float>(B, off);
+        ws.pri = carve<float>(B, off);
+        ws.bidx = carve<long>(B, off);
+        ws.at_h1 = carve<float>((long)B * H, off);
+        ws.at_h2 = carve<float>((long)B * H, off);
+        ws.at_h3 = carve<float>((long)B * H, off);
+        ws.a2 = carve<float>((long)B * A, off);
+        ws.ct_h1 = carve<float>((long)B * H, off);
+        ws.ct_h2 = carve<float>((long)B * H, off);
+        ws.ct_h3 = carve<float>((long)B * H, off);
+        ws.p_t = carve<float>((long)B * K, off);
+        ws.m_proj = carve<float>((long)B * K, off);
+        ws.c_h1 = carve<float>((long)B * H, off);
+        ws.c_h2 = carve<float>((long)B * H, off);
+        ws.c_h3 = carve<float>((long)B * H, off);
+        ws.q = carve<float>((long)B * K, off);
+        ws.dlog = carve<float>((long)B * K, off);
+        ws.d3 = carve<float>((long)B * H, off);
+        ws.d2 = carve<float>((long)B * H, off);
+        ws.d1 = carve<float>((long)B * H, off);
+        ws.da = carve<float>((long)B * A, off);
+        ws.pa_h1 = carve<float>((long)B * H, off);
+        ws.pa_h2 = carve<float>((long)B * H, off);
+        ws.pa_h3 = carve<float>((long)B * H, off);
+        ws.a_out = carve<float>((long)B * A, off);
+        ws.pc_h1 = carve<float>((long)B * H, off);
+        ws.pc_h2 = carve<float>((long)B * H, off);
+        ws.pc_h3 = carve<float>((long)B * H, off);
+        ws.pq = carve<float>((long)B * K, off);
+        ws.pd3 = carve<float>((long)B * K, off);
+        ws.pd2 = carve<float>((long)B * H, off);
+        ws.pdh1 = carve<float>((long)B * H, off);
+        ws.pda = carve<float>((long)B * A, off);
+        ws.adz = carve<float>((long)B * A, off);
+        ws.az1 = carve<float>((long)B * H, off);
+        ws.az2 = carve<float>((long)B * H, off);
+        ws.az3 = carve<float>((long)B * H, off);
         // split-K disjoint partials: the wide step's dW (max over layers of
         // ksplit * (weights + bias); the ksplit formula mirrors
         // launch_bwd's) and the MFMA heads' forward partials, which
@@ -254,8 +254,8 @@ public:
             for (int i = 0; i < 4; ++i) { need(anet.l[i]); need(cnet.l[i]); }
         }
         dw_parts = carve<float>(dwp, off);
-        gbar = carve<unsigned long long>(1536, off);
-        tstamp = carve<unsigned long long>(64, off);
+        ws.gbar = carve<unsigned long long>(1536, off);
+        ws.tstamp = carve<unsigned long long>(64, off);
         ing_s = carve<float>((long)ing_cap * O, off);
         ing_a = carve<float>((long)ing_cap * A, off);
         ing_r = carve<float>(ing_cap, off);
@@ -278,11 +278,12 @@ public:
         // on its first stateful call, prioritized_replay_memory.py:25-29).
         h.beta_t = 0;
         h.adam_t_actor = h.adam_t_critic = h.rng_epoch = 1;
-        HIP_CHECK(hipMemcpy(cnt, &h, sizeof(Counters), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ws.cnt, &h, sizeof(Counters),
+                            hipMemcpyHostToDevice));
         // min-tree neutral element is +inf (memset zero would make every
         // unoccupied leaf the minimum and zero out all IS weights)
         hipLaunchKernelGGL(k_fill_f64, dim3(1024), dim3(256), 0, nullptr,
-                           min_tree, 2 * tree_cap, HUGE_VAL);
+                           ws.min_tree, 2 * ws.tree_cap, HUGE_VAL);
         HIP_CHECK(hipDeviceSynchronize());
     }
 
@@ -441,67 +442,9 @@ public:
         return cfg.batch <= 512 ? PATH_ROWBLOCK : PATH_WIDE;
     }
 
-    PStepArgs ps_args() {
-        PStepArgs g{};
-        g.B = cfg.batch; g.O = cfg.obs; g.A = cfg.act; g.H = cfg.hidden;
-        g.K = cfg.atoms;
-        g.v_min = cfg.v_min; g.v_max = cfg.v_max; g.gamma_n = cfg.gamma_n;
-        g.per_eps = cfg.per_eps; g.tau = cfg.tau;
-        g.lr_actor = cfg.lr_actor; g.lr_critic = cfg.lr_critic;
-        g.per_alpha = cfg.per_alpha; g.per_beta0 = cfg.per_beta0;
-        g.per_beta_iters = (float)cfg.per_beta_iters;
-        g.is_weighting = cfg.is_weighting;
-        g.seed = cfg.seed; g.tree_cap = tree_cap;
-        g.n_actor = anet.n_params; g.n_critic = cnet.n_params;
-        for (int i = 0; i < 4; ++i) { g.al[i] = anet.l[i]; g.cl[i] = cnet.l[i]; }
-        g.p_actor = p_actor; g.p_actor_t = p_actor_t;
-        g.p_critic = p_critic; g.p_critic_t = p_critic_t;
-        g.g_actor = g_actor; g.g_critic = g_critic;
-        g.m_actor = m_actor; g.v_actor = v_actor;
-        g.m_critic = m_critic; g.v_critic = v_critic;
-        g.rs = rs; g.ra = ra; g.rr = rr; g.rs2 = rs2; g.rd = rd;
-        g.sum_tree = sum_tree; g.min_tree = min_tree;
-        g.bs = bs; g.bs_b = bs_b;
-        g.ba = ba; g.br = br; g.bs2 = bs2; g.bd = bd; g.bw = bw;
-        g.pri = pri; g.bidx = bidx;
-        g.at_h1 = at_h1; g.at_h2 = at_h2; g.at_h3 = at_h3; g.a2 = a2;
-        g.ct_h1 = ct_h1; g.ct_h2 = ct_h2; g.ct_h3 = ct_h3; g.p_t = p_t;
-        g.m_proj = m_proj;
-        g.c_h1 = c_h1; g.c_h2 = c_h2; g.c_h3 = c_h3; g.q = q;
-        g.dlog = dlog; g.d3 = d3; g.d2 = d2; g.d1 = d1;
-        g.pa_h1 = pa_h1; g.pa_h2 = pa_h2; g.pa_h3 = pa_h3; g.a_out = a_out;
-        g.pc_h1 = pc_h1; g.pc_h2 = pc_h2; g.pc_h3 = pc_h3; g.pq = pq;
-        g.pd3 = pd3; g.pd2 = pd2; g.pdh1 = pdh1; g.adz = adz;
-        g.az1 = az1; g.az2 = az2; g.az3 = az3;
-        g.cnt = cnt; g.gbar = gbar; g.tstamp = tstamp;
-        return g;
-    }
-
     void enqueue_persistent(int nsteps) {
-        PStepArgs g = ps_args();
         hipLaunchKernelGGL(k_step_persistent, dim3(PNWG), dim3(256), 0,
-                           stream, g, nsteps);
-    }
-
-    RowBlockArgs rb_args() {
-        RowBlockArgs g{};
-        g.B = cfg.batch; g.O = cfg.obs; g.A = cfg.act; g.H = cfg.hidden;
-        g.K = cfg.atoms;
-        g.v_min = cfg.v_min; g.v_max = cfg.v_max; g.gamma_n = cfg.gamma_n;
-        g.per_eps = cfg.per_eps; g.is_weighting = cfg.is_weighting;
-        g.p_actor = p_actor; g.p_actor_t = p_actor_t;
-        g.p_critic = p_critic; g.p_critic_t = p_critic_t;
-        for (int i = 0; i < 4; ++i) { g.al[i] = anet.l[i]; g.cl[i] = cnet.l[i]; }
-        g.bs = bs; g.ba = ba; g.br = br; g.bs2 = bs2; g.bd = bd; g.bw = bw;
-        g.a2 = a2; g.p_t = p_t; g.m_proj = m_proj; g.q = q; g.dlog = dlog;
-        g.pri = pri;
-        g.c_h1 = c_h1; g.c_h2 = c_h2; g.c_h3 = c_h3;
-        g.d1 = d1; g.d2 = d2; g.d3 = d3;
-        g.pa_h1 = pa_h1; g.pa_h2 = pa_h2; g.pa_h3 = pa_h3; g.a_out = a_out;
-        g.pc_h1 = pc_h1; g.pc_h2 = pc_h2; g.pc_h3 = pc_h3; g.pq = pq;
-        g.az1 = az1; g.az2 = az2; g.az3 = az3; g.adz = adz;
-        g.cnt = cnt;
-        return g;
+                           stream, ws, nsteps);
     }
 
     // All four layers' weight gradients of one net in a single k_bwd4
@@ -527,53 +470,53 @@ public:
 
     void launch_per_sample() {
         hipLaunchKernelGGL(k_per_sample, dim3(ceil_div(cfg.batch, 4)),
-            dim3(256), 0, stream,
-            sum_tree, min_tree, tree_cap, rs, ra, rr, rs2, rd,
-            cfg.obs, cfg.act, bs, ba, br, bs2, bd, bw, bidx, cfg.batch, cnt,
-            cfg.per_beta0, (float)cfg.per_beta_iters, cfg.seed);
+                           dim3(256), 0, stream, ws);
     }
 
     // Adam + target soft-update of one net, fused
     void launch_adam_lerp(bool is_actor) {
         if (is_actor)
             hipLaunchKernelGGL(k_adam_lerp, dim3(256), dim3(256), 0, stream,
-                               p_actor, g_actor, m_actor, v_actor,
-                               p_actor_t, anet.n_params, cfg.lr_actor,
-                               0.9f, 0.999f, 1e-8f, cfg.tau, cnt, 1);
+                               ws.p_actor, ws.g_actor, ws.m_actor, ws.v_actor,
+                               ws.p_actor_t, anet.n_params, cfg.lr_actor,
+                               0.9f, 0.999f, 1e-8f, cfg.tau, ws.cnt, 1);
         else
             hipLaunchKernelGGL(k_adam_lerp, dim3(256), dim3(256), 0, stream,
-                               p_critic, g_critic, m_critic, v_critic,
-                               p_critic_t, cnet.n_params, cfg.lr_critic,
-                               0.9f, 0.999f, 1e-8f, cfg.tau, cnt, 0);
+                               ws.p_critic, ws.g_critic, ws.m_critic,
+                               ws.v_critic, ws.p_critic_t, cnet.n_params,
+                               cfg.lr_critic, 0.9f, 0.999f, 1e-8f, cfg.tau,
+                               ws.cnt, 0);
     }
 
     void enqueue_step_rowblock(int mask) {
         const int B = cfg.batch, H = cfg.hidden;
         int row_wgs = ceil_div(B, 4);
         long smem = rb_lds_bytes(H);
-
-        RowBlockArgs g = rb_args();
         if (mask & PH_CRITIC_GRADS) {
             launch_per_sample();
             hipLaunchKernelGGL(k_critic_rowblock, dim3(row_wgs), dim3(256),
-                               smem, stream, g);
-            launch_dw4({{d1, bs, nullptr}, {d2, c_h1, ba},
-                        {d3, c_h2, nullptr}, {dlog, c_h3, nullptr}},
-                       cnet, g_critic);
+                               smem, stream, ws);
+            launch_dw4({{ws.d1, ws.bs, nullptr},
+                        {ws.d2, ws.c_h1, ws.ba},
+                        {ws.d3, ws.c_h2, nullptr},
+                        {ws.dlog, ws.c_h3, nullptr}},
+                       cnet, ws.g_critic);
         }
         if (mask & PH_CRITIC_APPLY) launch_adam_lerp(false);
         if (mask & PH_ACTOR_GRADS) {
             hipLaunchKernelGGL(k_policy_rowblock, dim3(row_wgs), dim3(256),
-                               smem, stream, g);
-            launch_dw4({{az1, bs, nullptr}, {az2, pa_h1, nullptr},
-                        {az3, pa_h2, nullptr}, {adz, pa_h3, nullptr}},
-                       anet, g_actor);
+                               smem, stream, ws);
+            launch_dw4({{ws.az1, ws.bs, nullptr},
+                        {ws.az2, ws.pa_h1, nullptr},
+                        {ws.az3, ws.pa_h2, nullptr},
+                        {ws.adz, ws.pa_h3, nullptr}},
+                       anet, ws.g_actor);
         }
         if (mask & PH_ACTOR_APPLY) {
             launch_adam_lerp(true);
             hipLaunchKernelGGL(k_per_update, dim3(1), dim3(256), 0, stream,
-                               sum_tree, min_tree, tree_cap, bidx, pri, B,
-                               cfg.per_alpha, cnt);
+                               ws.sum_tree, ws.min_tree, ws.tree_cap,
+                               ws.bidx, ws.pri, B, cfg.per_alpha, ws.cnt);
         }
     }
 
@@ -586,95 +529,97 @@ public:
         if (mask & PH_CRITIC_GRADS) {
         launch_per_sample();
         // P2: a_t.L1(s2) | c_t.L1(s2) | c.L1(s)
-        launch_fwd({fwd_job(bs2, nullptr, p_actor_t, anet.l[0], at_h1,
+        launch_fwd({fwd_job(ws.bs2, nullptr, ws.p_actor_t, anet.l[0], ws.at_h1,
                             ACT_RELU),
-                    fwd_job(bs2, nullptr, p_critic_t, cnet.l[0], ct_h1,
+                    fwd_job(ws.bs2, nullptr, ws.p_critic_t, cnet.l[0], ws.ct_h1,
                             ACT_RELU),
-                    fwd_job(bs, nullptr, p_critic, cnet.l[0], c_h1,
+                    fwd_job(ws.bs, nullptr, ws.p_critic, cnet.l[0], ws.c_h1,
                             ACT_RELU)});
         // P3: a_t.L2 | c.L2(cat c_h1, a)
-        launch_fwd({fwd_job(at_h1, nullptr, p_actor_t, anet.l[1], at_h2,
-                            ACT_NONE),
-                    fwd_job(c_h1, ba, p_critic, cnet.l[1], c_h2, ACT_RELU)});
+        launch_fwd({fwd_job(ws.at_h1, nullptr, ws.p_actor_t, anet.l[1],
+                            ws.at_h2, ACT_NONE),
+                    fwd_job(ws.c_h1, ws.ba, ws.p_critic, cnet.l[1], ws.c_h2,
+                            ACT_RELU)});
         // P4: a_t.L3 | c.L3
-        launch_fwd({fwd_job(at_h2, nullptr, p_actor_t, anet.l[2], at_h3,
-                            ACT_RELU),
-                    fwd_job(c_h2, nullptr, p_critic, cnet.l[2], c_h3,
+        launch_fwd({fwd_job(ws.at_h2, nullptr, ws.p_actor_t, anet.l[2],
+                            ws.at_h3, ACT_RELU),
+                    fwd_job(ws.c_h2, nullptr, ws.p_critic, cnet.l[2], ws.c_h3,
                             ACT_RELU)});
         // P5: a_t.L4 tanh | c.L4 softmax -> q
-        launch_fwd({fwd_job(at_h3, nullptr, p_actor_t, anet.l[3], a2,
+        launch_fwd({fwd_job(ws.at_h3, nullptr, ws.p_actor_t, anet.l[3], ws.a2,
                             ACT_TANH),
-                    fwd_job(c_h3, nullptr, p_critic, cnet.l[3], q,
+                    fwd_job(ws.c_h3, nullptr, ws.p_critic, cnet.l[3], ws.q,
                             ACT_SOFTMAX)});
         // P6-8: c_t.L2(cat ct_h1, a2), c_t.L3, c_t.L4 softmax -> p_t
-        launch_fwd({fwd_job(ct_h1, a2, p_critic_t, cnet.l[1], ct_h2,
+        launch_fwd({fwd_job(ws.ct_h1, ws.a2, ws.p_critic_t, cnet.l[1], ws.ct_h2,
                             ACT_RELU)});
-        launch_fwd({fwd_job(ct_h2, nullptr, p_critic_t, cnet.l[2], ct_h3,
-                            ACT_RELU)});
-        launch_fwd({fwd_job(ct_h3, nullptr, p_critic_t, cnet.l[3], p_t,
+        launch_fwd({fwd_job(ws.ct_h2, nullptr, ws.p_critic_t, cnet.l[2],
+                            ws.ct_h3, ACT_RELU)});
+        launch_fwd({fwd_job(ws.ct_h3, nullptr, ws.p_critic_t, cnet.l[3], ws.p_t,
                             ACT_SOFTMAX)});
         // P9+P10 fused: projection + CE grad + priorities
         hipLaunchKernelGGL(k_project_ce, dim3(min(row_wgs, 256)),
                            dim3(256),
                            waves_per_wg * 64 * sizeof(float), stream,
-                           p_t, br, bd, q, bw, m_proj, dlog, pri, cnt,
+                           ws.p_t, ws.br, ws.bd, ws.q, ws.bw, ws.m_proj,
+                           ws.dlog, ws.pri, ws.cnt,
                            B, K, cfg.v_min, cfg.v_max, cfg.gamma_n,
                            cfg.per_eps, cfg.is_weighting);
         // P11-14: critic backward L4..L1
-        launch_bwd(dlog, c_h3, nullptr, p_critic, g_critic, cnet.l[3],
-                   d3, nullptr, c_h3, ACT_RELU, true);
-        launch_bwd(d3, c_h2, nullptr, p_critic, g_critic, cnet.l[2],
-                   d2, nullptr, c_h2, ACT_RELU, true);
-        launch_bwd(d2, c_h1, ba, p_critic, g_critic, cnet.l[1],
-                   d1, nullptr, c_h1, ACT_RELU, true);
-        launch_bwd(d1, bs, nullptr, p_critic, g_critic, cnet.l[0],
+        launch_bwd(ws.dlog, ws.c_h3, nullptr, ws.p_critic, ws.g_critic,
+                   cnet.l[3], ws.d3, nullptr, ws.c_h3, ACT_RELU, true);
+        launch_bwd(ws.d3, ws.c_h2, nullptr, ws.p_critic, ws.g_critic, cnet.l[2],
+                   ws.d2, nullptr, ws.c_h2, ACT_RELU, true);
+        launch_bwd(ws.d2, ws.c_h1, ws.ba, ws.p_critic, ws.g_critic, cnet.l[1],
+                   ws.d1, nullptr, ws.c_h1, ACT_RELU, true);
+        launch_bwd(ws.d1, ws.bs, nullptr, ws.p_critic, ws.g_critic, cnet.l[0],
                    nullptr, nullptr, nullptr, ACT_NONE, true);
         }
         // P15: Adam critic + target soft-update fused
         if (mask & PH_CRITIC_APPLY) launch_adam_lerp(false);
         if (mask & PH_ACTOR_GRADS) {
         // P16: actor.L1(s) | critic'.L1(s)
-        launch_fwd({fwd_job(bs, nullptr, p_actor, anet.l[0], pa_h1,
+        launch_fwd({fwd_job(ws.bs, nullptr, ws.p_actor, anet.l[0], ws.pa_h1,
                             ACT_RELU),
-                    fwd_job(bs, nullptr, p_critic, cnet.l[0], pc_h1,
+                    fwd_job(ws.bs, nullptr, ws.p_critic, cnet.l[0], ws.pc_h1,
                             ACT_RELU)});
         // P17-19: actor L2, L3, L4
-        launch_fwd({fwd_job(pa_h1, nullptr, p_actor, anet.l[1], pa_h2,
+        launch_fwd({fwd_job(ws.pa_h1, nullptr, ws.p_actor, anet.l[1], ws.pa_h2,
                             ACT_NONE)});
-        launch_fwd({fwd_job(pa_h2, nullptr, p_actor, anet.l[2], pa_h3,
+        launch_fwd({fwd_job(ws.pa_h2, nullptr, ws.p_actor, anet.l[2], ws.pa_h3,
                             ACT_RELU)});
-        launch_fwd({fwd_job(pa_h3, nullptr, p_actor, anet.l[3], a_out,
+        launch_fwd({fwd_job(ws.pa_h3, nullptr, ws.p_actor, anet.l[3], ws.a_out,
                             ACT_TANH)});
         // P20-22: critic'(s, a_out)
-        launch_fwd({fwd_job(pc_h1, a_out, p_critic, cnet.l[1], pc_h2,
+        launch_fwd({fwd_job(ws.pc_h1, ws.a_out, ws.p_critic, cnet.l[1],
+                            ws.pc_h2, ACT_RELU)});
+        launch_fwd({fwd_job(ws.pc_h2, nullptr, ws.p_critic, cnet.l[2], ws.pc_h3,
                             ACT_RELU)});
-        launch_fwd({fwd_job(pc_h2, nullptr, p_critic, cnet.l[2], pc_h3,
-                            ACT_RELU)});
-        launch_fwd({fwd_job(pc_h3, nullptr, p_critic, cnet.l[3], pq,
+        launch_fwd({fwd_job(ws.pc_h3, nullptr, ws.p_critic, cnet.l[3], ws.pq,
                             ACT_SOFTMAX)});
         // P23: policy head gradient
         hipLaunchKernelGGL(k_policy_grad, dim3(min(row_wgs, 256)),
                            dim3(256), 0, stream,
-                           pq, pd3, cnt, B, K, cfg.v_min, cfg.v_max);
+                           ws.pq, ws.pd3, ws.cnt, B, K, cfg.v_min, cfg.v_max);
         // P24-26: dX back through critic' (no dW), ending at da
-        launch_bwd(pd3, pc_h3, nullptr, p_critic, nullptr, cnet.l[3],
-                   pd2, nullptr, pc_h3, ACT_RELU, false);
-        launch_bwd(pd2, pc_h2, nullptr, p_critic, nullptr, cnet.l[2],
-                   pdh1, nullptr, pc_h2, ACT_RELU, false);
-        launch_bwd(pdh1, pc_h1, a_out, p_critic, nullptr, cnet.l[1],
-                   nullptr, pda, pc_h1, ACT_RELU, false);
+        launch_bwd(ws.pd3, ws.pc_h3, nullptr, ws.p_critic, nullptr, cnet.l[3],
+                   ws.pd2, nullptr, ws.pc_h3, ACT_RELU, false);
+        launch_bwd(ws.pd2, ws.pc_h2, nullptr, ws.p_critic, nullptr, cnet.l[2],
+                   ws.pdh1, nullptr, ws.pc_h2, ACT_RELU, false);
+        launch_bwd(ws.pdh1, ws.pc_h1, ws.a_out, ws.p_critic, nullptr, cnet.l[1],
+                   nullptr, ws.pda, ws.pc_h1, ACT_RELU, false);
         // P27: tanh backward at actor output
         hipLaunchKernelGGL(k_tanh_bwd, dim3(ceil_div((long)B * cfg.act, 256)),
-                           dim3(256), 0, stream, pda, a_out, adz,
+                           dim3(256), 0, stream, ws.pda, ws.a_out, ws.adz,
                            (long)B * cfg.act);
         // P28-31: actor backward L4..L1 (with dW)
-        launch_bwd(adz, pa_h3, nullptr, p_actor, g_actor, anet.l[3],
-                   pd2 /*reuse*/, nullptr, pa_h3, ACT_RELU, true);
-        launch_bwd(pd2, pa_h2, nullptr, p_actor, g_actor, anet.l[2],
-                   pdh1, nullptr, pa_h2, ACT_NONE, true);
-        launch_bwd(pdh1, pa_h1, nullptr, p_actor, g_actor, anet.l[1],
-                   pd2, nullptr, pa_h1, ACT_RELU, true);
-        launch_bwd(pd2, bs, nullptr, p_actor, g_actor, anet.l[0],
+        launch_bwd(ws.adz, ws.pa_h3, nullptr, ws.p_actor, ws.g_actor, anet.l[3],
+                   ws.pd2 /*reuse*/, nullptr, ws.pa_h3, ACT_RELU, true);
+        launch_bwd(ws.pd2, ws.pa_h2, nullptr, ws.p_actor, ws.g_actor, anet.l[2],
+                   ws.pdh1, nullptr, ws.pa_h2, ACT_NONE, true);
+        launch_bwd(ws.pdh1, ws.pa_h1, nullptr, ws.p_actor, ws.g_actor,
+                   anet.l[1], ws.pd2, nullptr, ws.pa_h1, ACT_RELU, true);
+        launch_bwd(ws.pd2, ws.bs, nullptr, ws.p_actor, ws.g_actor, anet.l[0],
                    nullptr, nullptr, nullptr, ACT_NONE, true);
         }
         if (!(mask & PH_ACTOR_APPLY)) return;
@@ -684,19 +629,20 @@ public:
         // P34: PER priority write-back by the per-level grid-wide repair
         // (the one-wg level-synced k_per_update serializes at this size)
         hipLaunchKernelGGL(k_per_leaves, dim3(ceil_div(B, 256)),
-                           dim3(256), 0, stream, sum_tree, min_tree,
-                           tree_cap, bidx, pri, B, cfg.per_alpha, cnt);
+                           dim3(256), 0, stream, ws.sum_tree, ws.min_tree,
+                           ws.tree_cap, ws.bidx, ws.pri, B, cfg.per_alpha,
+                           ws.cnt);
         long levels = 0;
-        for (long c = tree_cap; c > 1; c >>= 1) ++levels;
+        for (long c = ws.tree_cap; c > 1; c >>= 1) ++levels;
         // 4 heights per dispatch (k_per_level4): 20 launches -> 5
         for (long h0 = 0; h0 < levels; h0 += 4) {
             int nlv = (int)((levels - h0) < 4 ? (levels - h0) : 4);
             hipLaunchKernelGGL(k_per_level4,
                                dim3(ceil_div((long)B * nlv, 256)),
-                               dim3(256), 0, stream, sum_tree, min_tree,
-                               tree_cap, bidx, B, h0, nlv);
+                               dim3(256), 0, stream, ws.sum_tree, ws.min_tree,
+                               ws.tree_cap, ws.bidx, B, h0, nlv);
         }
-        hipLaunchKernelGGL(k_tick_end, dim3(1), dim3(64), 0, stream, cnt);
+        hipLaunchKernelGGL(k_tick_end, dim3(1), dim3(64), 0, stream, ws.cnt);
     }
 
     void enqueue_step(int mask = PH_ALL) {
@@ -763,19 +709,19 @@ public:
     void synth_fill(long n, uint64_t seed) {
         if (n > cfg.capacity) n = cfg.capacity;
         hipLaunchKernelGGL(k_synth_fill, dim3(1024), dim3(256), 0, stream,
-                           rs, ra, rr, rs2, rd, sum_tree, min_tree, tree_cap,
-                           cfg.capacity, n, cfg.obs, cfg.act, seed,
-                           cfg.per_alpha);
-        for (long lo = tree_cap / 2; lo >= 1; lo /= 2)
+                           ws.rs, ws.ra, ws.rr, ws.rs2, ws.rd, ws.sum_tree,
+                           ws.min_tree, ws.tree_cap, cfg.capacity, n, cfg.obs,
+                           cfg.act, seed, cfg.per_alpha);
+        for (long lo = ws.tree_cap / 2; lo >= 1; lo /= 2)
             hipLaunchKernelGGL(k_tree_build_level, dim3(256), dim3(256), 0,
-                               stream, sum_tree, min_tree, lo,
+                               stream, ws.sum_tree, ws.min_tree, lo,
                                lo == 0 ? 1 : 2 * lo);
         Counters h{};
-        HIP_CHECK(hipMemcpyAsync(&h, cnt, sizeof(h), hipMemcpyDeviceToHost,
+        HIP_CHECK(hipMemcpyAsync(&h, ws.cnt, sizeof(h), hipMemcpyDeviceToHost,
                                  stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         h.size = n; h.pos = n % cfg.capacity; h.max_priority = 1.0f;
-        HIP_CHECK(hipMemcpy(cnt, &h, sizeof(h), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ws.cnt, &h, sizeof(h), hipMemcpyHostToDevice));
     }
 
     void ingest(const float* hs, const float* ha, const float* hr,
@@ -794,30 +740,32 @@ public:
                                  hipMemcpyHostToDevice, stream));
         if (T <= 4096) {
             hipLaunchKernelGGL(k_replay_add, dim3(1), dim3(1024), 0, stream,
-                               rs, ra, rr, rs2, rd, sum_tree, min_tree,
-                               tree_cap, cfg.capacity, ing_s, ing_a, ing_r,
-                               ing_s2, ing_d, T, O, A, cfg.per_alpha, cnt);
+                               ws.rs, ws.ra, ws.rr, ws.rs2, ws.rd,
+                               ws.sum_tree, ws.min_tree, ws.tree_cap,
+                               cfg.capacity, ing_s, ing_a, ing_r,
+                               ing_s2, ing_d, T, O, A, cfg.per_alpha, ws.cnt);
         } else {
             // bulk path: grid-wide copy + leaf init, then a full
             // bandwidth-bound tree rebuild (far cheaper than one wg
             // chasing 20-level paths for 100k rows)
             Counters h{};
-            HIP_CHECK(hipMemcpyAsync(&h, cnt, sizeof(h),
+            HIP_CHECK(hipMemcpyAsync(&h, ws.cnt, sizeof(h),
                                      hipMemcpyDeviceToHost, stream));
             HIP_CHECK(hipStreamSynchronize(stream));
             double pa = pow((double)h.max_priority, (double)cfg.per_alpha);
             hipLaunchKernelGGL(k_replay_copy, dim3(1024), dim3(256), 0,
-                               stream, rs, ra, rr, rs2, rd, sum_tree,
-                               min_tree, tree_cap, cfg.capacity, h.pos,
+                               stream, ws.rs, ws.ra, ws.rr, ws.rs2, ws.rd,
+                               ws.sum_tree, ws.min_tree, ws.tree_cap,
+                               cfg.capacity, h.pos,
                                ing_s, ing_a, ing_r, ing_s2, ing_d, T, O, A,
                                pa);
-            for (long lo = tree_cap / 2; lo >= 1; lo >>= 1)
+            for (long lo = ws.tree_cap / 2; lo >= 1; lo >>= 1)
                 hipLaunchKernelGGL(k_tree_build_level, dim3(1024),
-                                   dim3(256), 0, stream, sum_tree,
-                                   min_tree, lo, 2 * lo);
+                                   dim3(256), 0, stream, ws.sum_tree,
+                                   ws.min_tree, lo, 2 * lo);
             h.pos = (h.pos + T) % cfg.capacity;
             h.size = h.size + T > cfg.capacity ? cfg.capacity : h.size + T;
-            HIP_CHECK(hipMemcpyAsync(cnt, &h, sizeof(h),
+            HIP_CHECK(hipMemcpyAsync(ws.cnt, &h, sizeof(h),
                                      hipMemcpyHostToDevice, stream));
         }
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -833,7 +781,7 @@ public:
 
     Counters read_counters() {
         Counters h{};
-        HIP_CHECK(hipMemcpy(&h, cnt, sizeof(h), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&h, ws.cnt, sizeof(h), hipMemcpyDeviceToHost));
         // adam/rng counters are pre-advanced for the NEXT step (init 1 so
         // the first step sees t=1); report steps COMPLETED to the host.
         // beta_t starts at 0 (LinearSchedule value_at(0) on the first
@@ -903,10 +851,10 @@ public:
         a.ep_state = (long long*)(base + o_ep);
         r_h1 = (float*)(base + o_h1); r_h2 = (float*)(base + o_h2);
         r_h3 = (float*)(base + o_h3);
-        a.rs = rs; a.ra = ra; a.rr = rr; a.rs2 = rs2; a.rd = rd;
-        a.sum_tree = sum_tree; a.min_tree = min_tree;
-        a.tree_cap = tree_cap; a.capacity = cfg.capacity;
-        a.cnt = cnt;
+        a.rs = ws.rs; a.ra = ws.ra; a.rr = ws.rr; a.rs2 = ws.rs2; a.rd = ws.rd;
+        a.sum_tree = ws.sum_tree; a.min_tree = ws.min_tree;
+        a.tree_cap = ws.tree_cap; a.capacity = cfg.capacity;
+        a.cnt = ws.cnt;
         roll_ = a;
         roll_emits_per_ep = horizon - nsteps + 1;
     }
@@ -917,7 +865,7 @@ public:
         // head pair: dw_parts is sized for the learner batch, not for M)
         auto run = [&](const float* x, const LayerDesc& l, float* y,
                        int actk) {
-            FwdJob j = fwd_job(x, nullptr, p_actor, l, y, actk, M);
+            FwdJob j = fwd_job(x, nullptr, ws.p_actor, l, y, actk, M);
             if (fwd_uses_mfma(M)) launch_fwd_mfma(j);
             else launch_fwd_valu(j);
         };
@@ -947,9 +895,9 @@ public:
                            (long)emit_k * a.M);
         // internal tree nodes: one bandwidth-bound full sweep per episode
         // (vs horizon x per-path repair) — leaves were set at emit
-        for (long lo = tree_cap / 2; lo >= 1; lo >>= 1)
+        for (long lo = ws.tree_cap / 2; lo >= 1; lo >>= 1)
             hipLaunchKernelGGL(k_tree_build_level, dim3(1024), dim3(256), 0,
-                               stream, sum_tree, min_tree, lo, 2 * lo);
+                               stream, ws.sum_tree, ws.min_tree, lo, 2 * lo);
     }
 
     void rollout_run(int episodes, bool reset, bool use_graph) {
@@ -994,17 +942,17 @@ public:
     void actor_forward(const float* hx, float* hy, int n) {
         // reuse batch buffers (requires n <= batch)
         if (n > cfg.batch) throw std::runtime_error("actor_forward: n > batch");
-        HIP_CHECK(hipMemcpyAsync(bs, hx, (long)n * cfg.obs * 4,
+        HIP_CHECK(hipMemcpyAsync(ws.bs, hx, (long)n * cfg.obs * 4,
                                  hipMemcpyHostToDevice, stream));
-        launch_fwd({fwd_job(bs, nullptr, p_actor, anet.l[0], pa_h1,
+        launch_fwd({fwd_job(ws.bs, nullptr, ws.p_actor, anet.l[0], ws.pa_h1,
                             ACT_RELU)});
-        launch_fwd({fwd_job(pa_h1, nullptr, p_actor, anet.l[1], pa_h2,
+        launch_fwd({fwd_job(ws.pa_h1, nullptr, ws.p_actor, anet.l[1], ws.pa_h2,
                             ACT_NONE)});
-        launch_fwd({fwd_job(pa_h2, nullptr, p_actor, anet.l[2], pa_h3,
+        launch_fwd({fwd_job(ws.pa_h2, nullptr, ws.p_actor, anet.l[2], ws.pa_h3,
                             ACT_RELU)});
-        launch_fwd({fwd_job(pa_h3, nullptr, p_actor, anet.l[3], a_out,
+        launch_fwd({fwd_job(ws.pa_h3, nullptr, ws.p_actor, anet.l[3], ws.a_out,
                             ACT_TANH)});
-        HIP_CHECK(hipMemcpyAsync(hy, a_out, (long)n * cfg.act * 4,
+        HIP_CHECK(hipMemcpyAsync(hy, ws.a_out, (long)n * cfg.act * 4,
                                  hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
     }

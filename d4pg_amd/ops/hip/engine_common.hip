@@ -1,5 +1,7 @@
-// Common types (layer geometry, config, device counters), the philox RNG and
-// the small device helpers every path shares.  Used by all other parts.
+// Common types (layer geometry, config, device counters, the StepArgs block
+// every train-step kernel takes), the philox RNG and the small device helpers
+// every path shares.  Used by all other parts; the step's row and probe
+// formulas follow in engine_rowmath.hip.
 //
 // Numerics: fp32 end-to-end, matching the reference's CPU fp32; per-thread
 // dot products accumulate in ascending-k order so every path agrees with
@@ -96,21 +98,6 @@ struct Counters {
 // max fan-in a fwd workgroup stages (hidden(1024) + act margin)
 #define FWD_XMAX 1032
 
-// ---- C51 bin split shared by every projection copy --------------------------
-// Fractional bin position b of a clamped Tz and its two neighbour bins l < u.
-// In float32 (v_max - v_min) / delta can round ABOVE K-1 (e.g. 27.000002 at
-// K=28 on [-300, 0]); uncapped, ceil(b) = K indexes one float past the row.
-// Capping b at K-1 leaves every in-range value bit-identical.  Equal-bin
-// handling as in algo/projection.py (index-adjust so weights become (0,1)).
-__device__ __forceinline__ float c51_bins(float tz, float v_min, float delta,
-                                          int K, int& l, int& u) {
-    float b = fminf((tz - v_min) / delta, (float)(K - 1));
-    l = (int)floorf(b);
-    u = (int)ceilf(b);
-    if (l == u) { if (u > 0) l -= 1; else u += 1; }
-    return b;
-}
-
 __device__ inline float act_mask(int act, float h) {
     if (act == ACT_RELU) return h > 0.f ? 1.f : 0.f;
     if (act == ACT_TANH) return 1.f - h * h;
@@ -126,5 +113,44 @@ __device__ inline NetPtrs net_ptrs(const float* slab, const LayerDesc* l) {
             slab + l[2].w_off, slab + l[2].b_off,
             slab + l[3].w_off, slab + l[3].b_off};
 }
+
+// Everything a train step reads or writes on the device: geometry and
+// hyper-parameters (filled once by the Engine constructor) and the workspace
+// pointers (carved by Engine::layout).  The one argument of k_step_persistent,
+// k_critic_rowblock, k_policy_rowblock and k_per_sample; the wide path's
+// per-layer launches read single fields.
+struct StepArgs {
+    int B, O, A, H, K;
+    float v_min, v_max, gamma_n, per_eps, tau, lr_actor, lr_critic;
+    float per_alpha, per_beta0, per_beta_iters;
+    int is_weighting;
+    uint64_t seed;
+    long tree_cap;
+    long n_actor, n_critic;
+    LayerDesc al[4], cl[4];
+    // params / grads / moments / targets
+    float *p_actor, *p_actor_t, *p_critic, *p_critic_t;
+    float *g_actor, *g_critic, *m_actor, *v_actor, *m_critic, *v_critic;
+    // replay + trees
+    float *rs, *ra, *rr, *rs2, *rd;
+    double *sum_tree, *min_tree;
+    // batch (bs is double-buffered on the persistent path: the policy-block
+    // tail pre-samples the NEXT step's batch while this step's bs is still
+    // read by the policy forward and the actor dW)
+    float *bs, *bs_b, *ba, *br, *bs2, *bd, *bw, *pri;
+    long *bidx;
+    // activations / deltas workspace
+    float *at_h1, *at_h2, *at_h3, *a2;              // actor_target path
+    float *ct_h1, *ct_h2, *ct_h3, *p_t, *m_proj;    // critic_target path
+    float *c_h1, *c_h2, *c_h3, *q, *dlog, *d3, *d2, *d1;   // critic + deltas
+    float *pa_h1, *pa_h2, *pa_h3, *a_out;           // actor (policy) path
+    float *pc_h1, *pc_h2, *pc_h3, *pq;              // critic(s, actor(s))
+    float *pd3, *pd2, *pdh1, *adz, *az1, *az2, *az3;    // policy deltas
+    Counters* cnt;
+    unsigned long long* gbar;        // persistent grid barrier state
+    unsigned long long* tstamp;      // [64] per-phase s_memrealtime stamps
+    float *da, *pda;                 // action-slice deltas (wide path)
+};
+
 
 }  // namespace d4pg

@@ -63,21 +63,18 @@ __global__ void k_fwd(FwdJob j) {
     }
     if (j.act == ACT_SOFTMAX) {
         // one wave handles one row (TO==64 lanes over out<=64 columns)
-        float v = (b < j.B && o < j.out) ? acc : -INFINITY;
-        float mx = v;
-        for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-        float e = (b < j.B && o < j.out) ? __expf(v - mx) : 0.f;
-        float sum = e;
-        for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s, 64);
-        if (b < j.B && o < j.out) j.y[(long)b * j.out + o] = e / sum;
+        bool valid = b < j.B && o < j.out;
+        float sm = softmax_wave(acc, valid);
+        if (valid) j.y[(long)b * j.out + o] = sm;
     } else if (b < j.B && o < j.out) {
         j.y[(long)b * j.out + o] = acc;
     }
 }
 
 // ---- fused C51 projection + CE grad + priorities (wide path) ----------------
-// (the persistent path fuses these in p_project_ce; this is the standalone
-// twin for the per-layer/MFMA path — saves a launch + the m round-trip)
+// One wave per row over c51_project_row + ce_grad_row, the formulas the
+// persistent p_project_ce and k_critic_rowblock run too; fusing the two saves
+// a launch + the m round-trip.
 __global__ void k_project_ce(const float* __restrict__ p_t,
                              const float* __restrict__ r,
                              const float* __restrict__ d,
@@ -101,37 +98,20 @@ __global__ void k_project_ce(const float* __restrict__ p_t,
     // at B=4096 (4096 same-address RMWs)
     for (int row = blockIdx.x * wpb + wrow; row < B;
          row += gridDim.x * wpb) {
-    mrow[lane] = 0.f;
-    __builtin_amdgcn_wave_barrier();
-    if (row < B && lane < K) {
-        float delta = (v_max - v_min) / (K - 1);
-        float z = v_min + lane * delta;
-        float tz = r[row] + gamma_n * (1.f - d[row]) * z;
-        tz = fminf(v_max, fmaxf(v_min, tz));
-        int l, u;
-        float b = c51_bins(tz, v_min, delta, K, l, u);
-        float p = p_t[(long)row * K + lane];
-        atomicAdd(&mrow[l], p * ((float)u - b));
-        atomicAdd(&mrow[u], p * (b - (float)l));
-    }
-    __builtin_amdgcn_wave_barrier();
-    float mv = (lane < K) ? mrow[lane] : 0.f;
-    float qv = (lane < K) ? q[(long)row * K + lane] : 0.f;
-    if (lane < K) m_out[(long)row * K + lane] = mv;
-    float dot = mv * qv;
-    float ce = -mv * __logf(qv + 1e-10f);
-    for (int ss = 32; ss > 0; ss >>= 1) {
-        dot += __shfl_xor(dot, ss, 64);
-        ce += __shfl_xor(ce, ss, 64);
-    }
-    float scale = (is_weighting && w) ? w[row] : 1.f;
-    if (lane < K)
-        dlogits[(long)row * K + lane] = scale * (qv - mv) / (float)B;
-    if (lane == 0) {
-        pri[row] = dot + per_eps;
-        ce_acc += scale * ce / (float)B;
-    }
-    __builtin_amdgcn_wave_barrier();
+        float p = (lane < K) ? p_t[(long)row * K + lane] : 0.f;
+        c51_project_row(mrow, p, r[row], d[row], v_min, v_max, gamma_n, K,
+                        lane);
+        float mv = (lane < K) ? mrow[lane] : 0.f;
+        float qv = (lane < K) ? q[(long)row * K + lane] : 0.f;
+        if (lane < K) m_out[(long)row * K + lane] = mv;
+        float scale = (is_weighting && w) ? w[row] : 1.f;
+        CeRow g = ce_grad_row(mv, qv, scale, B);
+        if (lane < K) dlogits[(long)row * K + lane] = g.dz;
+        if (lane == 0) {
+            pri[row] = g.dot + per_eps;
+            ce_acc += scale * g.ce / (float)B;
+        }
+        __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
     if (lane == 0) loss_red[wrow] = ce_acc;
@@ -144,7 +124,6 @@ __global__ void k_project_ce(const float* __restrict__ p_t,
 }
 
 // ---- policy gradient through the softmax head (K6 seed) ---------------------
-// L = -(1/B) sum_b sum_k q_k z_k  =>  dlogits_j = -q_j (z_j - E_q[z]) / B
 __global__ void k_policy_grad(const float* __restrict__ q,
                               float* __restrict__ dlogits,
                               Counters* cnt,
@@ -154,16 +133,14 @@ __global__ void k_policy_grad(const float* __restrict__ q,
     int wpb = blockDim.x / 64;
     __shared__ float loss_red[8];
     float loss_acc = 0.f;
-    float delta = (v_max - v_min) / (K - 1);
-    float z = v_min + lane * delta;
+    float z = c51_atom(v_min, v_max, K, lane);
     // grid-stride rows + one per-wg loss atomic (see k_project_ce)
     for (int row = blockIdx.x * wpb + wrow; row < B;
          row += gridDim.x * wpb) {
         float qv = (lane < K) ? q[(long)row * K + lane] : 0.f;
-        float e = qv * z;
-        for (int s = 32; s > 0; s >>= 1) e += __shfl_xor(e, s, 64);
-        if (lane < K)
-            dlogits[(long)row * K + lane] = -qv * (z - e) / (float)B;
+        float e;
+        float dz = policy_grad_row(qv, z, B, e);
+        if (lane < K) dlogits[(long)row * K + lane] = dz;
         if (lane == 0) loss_acc += -e / (float)B;
     }
     __syncthreads();
@@ -187,22 +164,22 @@ __global__ void k_tanh_bwd(const float* __restrict__ da,
     }
 }
 
-// ---- fused Adam + target soft-update in one pass (row-block path) ----------
+// ---- fused Adam + target soft-update in one pass (row-block, wide) ---------
+// (the element update is written out here and in p_adam_lerp, see adam_bias)
 __global__ void k_adam_lerp(float* __restrict__ p, const float* __restrict__ g,
                             float* __restrict__ m, float* __restrict__ v,
                             float* __restrict__ tgt, long n, float lr,
                             float b1, float b2, float eps, float tau,
                             const Counters* cnt, int is_actor) {
-    long long t = is_actor ? cnt->adam_t_actor : cnt->adam_t_critic;
-    float bc1 = 1.f - __powf(b1, (float)t);
-    float bc2 = 1.f - __powf(b2, (float)t);
+    AdamBias bc = adam_bias(b1, b2, is_actor ? cnt->adam_t_actor
+                                             : cnt->adam_t_critic);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long)gridDim.x * blockDim.x) {
         float gi = g[i];
         float mi = b1 * m[i] + (1.f - b1) * gi;
         float vi = b2 * v[i] + (1.f - b2) * gi * gi;
         m[i] = mi; v[i] = vi;
-        float pn = p[i] - lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
+        float pn = p[i] - lr * (mi / bc.bc1) / (sqrtf(vi / bc.bc2) + eps);
         p[i] = pn;
         tgt[i] += tau * (pn - tgt[i]);
     }

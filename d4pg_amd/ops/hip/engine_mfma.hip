@@ -233,7 +233,7 @@ __global__ void k_dx_narrow(const float* __restrict__ dz,
 }
 
 // Head finish: y[row] = act(sum_seg parts[seg][row] + bias), wave == row
-// (out <= 64); softmax reduces across the wave like k_fwd's epilogue.
+// (out <= 64); softmax reduces across the wave (softmax_wave).
 __global__ void k_head_finish(const float* __restrict__ parts,
                               const float* __restrict__ bias,
                               float* __restrict__ y, int B, int out,
@@ -249,14 +249,8 @@ __global__ void k_head_finish(const float* __restrict__ parts,
             v += bias[lane];
         }
         if (act_kind == ACT_SOFTMAX) {
-            float mx = (lane < out) ? v : -INFINITY;
-            for (int s = 32; s > 0; s >>= 1)
-                mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-            float e = (lane < out) ? __expf(v - mx) : 0.f;
-            float sum = e;
-            for (int s = 32; s > 0; s >>= 1)
-                sum += __shfl_xor(sum, s, 64);
-            if (lane < out) y[(long)row * out + lane] = e / sum;
+            float sm = softmax_wave(v, lane < out);
+            if (lane < out) y[(long)row * out + lane] = sm;
         } else if (lane < out) {
             if (act_kind == ACT_RELU) v = fmaxf(v, 0.f);
             else if (act_kind == ACT_TANH) v = tanhf(v);

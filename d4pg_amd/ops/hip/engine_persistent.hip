@@ -42,40 +42,8 @@ namespace d4pg {
 // LDS pool, 12864 floats.  The largest user is p_dw2 (two [64][68] slices =
 // 8704 floats); p_fwd / p_bwd_dx need PWOFF + 64 * 68 = 6400.  The other
 // 4160 floats are slack: nothing uses them, and shrinking the pool would
-// change the kernel's LDS footprint (52,480 B with p_per_update's smax).
+// change the kernel's LDS footprint (52,480 B with per_write_leaves' smax).
 #define PLDS_FLOATS (2 * 4 * PXMAX + 2 * 64 * 68 + 64)
-
-struct PStepArgs {
-    int B, O, A, H, K;
-    float v_min, v_max, gamma_n, per_eps, tau, lr_actor, lr_critic;
-    float per_alpha, per_beta0, per_beta_iters;
-    int is_weighting;
-    uint64_t seed;
-    long tree_cap;
-    long n_actor, n_critic;
-    LayerDesc al[4], cl[4];
-    // params / grads / moments / targets
-    float *p_actor, *p_actor_t, *p_critic, *p_critic_t;
-    float *g_actor, *g_critic, *m_actor, *v_actor, *m_critic, *v_critic;
-    // replay + trees
-    const float *rs, *ra, *rr, *rs2, *rd;
-    double *sum_tree, *min_tree;
-    // batch (bs is double-buffered: the policy-block tail pre-samples
-    // the NEXT step's batch while this step's bs is still read by the
-    // policy forward and the actor dW)
-    float *bs, *bs_b, *ba, *br, *bs2, *bd, *bw, *pri;
-    long *bidx;
-    // activations / deltas workspace
-    float *at_h1, *at_h2, *at_h3, *a2;
-    float *ct_h1, *ct_h2, *ct_h3, *p_t, *m_proj;
-    float *c_h1, *c_h2, *c_h3, *q, *dlog, *d3, *d2, *d1;
-    float *pa_h1, *pa_h2, *pa_h3, *a_out;
-    float *pc_h1, *pc_h2, *pc_h3, *pq;
-    float *pd3, *pd2, *pdh1, *adz, *az1, *az2, *az3;
-    Counters* cnt;
-    unsigned long long* gbar;        // [0] = arrival counter, [1] = base
-    unsigned long long* tstamp;      // [64] per-phase s_memrealtime stamps
-};
 
 // phase timing probe: wg0/lane0 stamps the wall clock (100 MHz constant
 // clock) after each barrier of the FIRST step of a launch; read back via
@@ -308,7 +276,10 @@ __device__ __noinline__ void p_fwd(float* lds, const float* x1, const float* x2,
             __syncthreads();
         }
         if (act_kind == ACT_SOFTMAX) {
-            // out <= 64, single col-chunk; wave == one row
+            // out <= 64, single col-chunk; wave == one row.  This is
+            // softmax_wave written out: calling the helper here changes
+            // p_fwd's code enough to cost the flagship step 0.8% (measured,
+            // 4,255 vs 4,288 steps/s), with equal results.
             float v = (o < out) ? acc + bias[o] : -INFINITY;
             float mx = v;
             for (int s = 32; s > 0; s >>= 1)
@@ -539,8 +510,7 @@ __device__ inline void p_adam_lerp(float* __restrict__ p,
                                    float lr, float tau, long long t,
                                    int nwg = PNWG) {
     const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    float bc1 = 1.f - __powf(b1, (float)t);
-    float bc2 = 1.f - __powf(b2, (float)t);
+    AdamBias bc = adam_bias(b1, b2, t);
     // register-batched: fire all 5 streams' loads for 4 grid-strides at
     // once (a serial load->compute->store loop pays one memory round-trip
     // per element batch)
@@ -562,19 +532,22 @@ __device__ inline void p_adam_lerp(float* __restrict__ p,
         for (int u = 0; u < 4; ++u) {
             long i = base + u * stride;
             if (i >= n) continue;
+            // k_adam_lerp's element update, written out in both (see
+            // adam_bias for why it is not one helper)
             float gi = gi_[u];
             float mi = b1 * mi_[u] + (1.f - b1) * gi;
             float vi = b2 * vi_[u] + (1.f - b2) * gi * gi;
             m[i] = mi; v[i] = vi;
-            float pn = pi_[u] - lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
+            float pn = pi_[u] - lr * (mi / bc.bc1)
+                                   / (sqrtf(vi / bc.bc2) + eps);
             p[i] = pn;
             tgt_slab[i] = ti_[u] + tau * (pn - ti_[u]);
         }
     }
 }
 
-// PER sample + gather phase (k_per_sample semantics; one wave per probe)
-__device__ inline void p_sample(const PStepArgs& g, int wg0,
+// PER sample + gather phase (one wave per probe, like k_per_sample)
+__device__ inline void p_sample(const StepArgs& g, int wg0,
                                 long long epoch, long long beta_t,
                                 float* bs_out) {
     // wg0: first workgroup of the sampling crew.  epoch / beta_t: the
@@ -586,122 +559,42 @@ __device__ inline void p_sample(const PStepArgs& g, int wg0,
     int probe = ((int)blockIdx.x - wg0) * 4 + (threadIdx.x >> 6);
     int lane = threadIdx.x & 63;
     if (probe >= g.B) return;
-    long long n = g.cnt->size;
-    double total = g.sum_tree[1];
-    float frac = fminf((float)((double)beta_t / g.per_beta_iters), 1.0f);
-    float beta = g.per_beta0 + frac * (1.0f - g.per_beta0);
-    long idx;
-    if (lane == 0) {
-        Philox4 r = philox4(g.seed, (uint64_t)epoch, (uint64_t)probe);
-        double mass = (double)u01(r.v[0]) * total;
-        long node = 1;
-        // 4-ary descent over the binary layout (see k_per_sample): two
-        // binary levels per contiguous grandchildren load, bit-exact leaf
-        // choice.  Deep levels are random-access, once-per-step: bypass
-        // L2 for them, keep the hot top of the tree cached.
-        while (node < g.tree_cap / 2) {
-            long gb = 4 * node;
-            double g0, g1, g2;
-            if (gb >= 16384) {
-                g0 = __builtin_nontemporal_load(&g.sum_tree[gb]);
-                g1 = __builtin_nontemporal_load(&g.sum_tree[gb + 1]);
-                g2 = __builtin_nontemporal_load(&g.sum_tree[gb + 2]);
-            } else {
-                g0 = g.sum_tree[gb];
-                g1 = g.sum_tree[gb + 1];
-                g2 = g.sum_tree[gb + 2];
-            }
-            double s01 = g0 + g1;
-            if (mass <= s01) {
-                if (mass <= g0) node = gb;
-                else { mass -= g0; node = gb + 1; }
-            } else {
-                mass -= s01;
-                if (mass <= g2) node = gb + 2;
-                else { mass -= g2; node = gb + 3; }
-            }
-        }
-        if (node < g.tree_cap) {               // odd final level
-            double ls = (node >= 16384)
-                ? __builtin_nontemporal_load(&g.sum_tree[2 * node])
-                : g.sum_tree[2 * node];
-            if (mass > ls) { mass -= ls; node = 2 * node + 1; }
-            else           { node = 2 * node; }
-        }
-        idx = node - g.tree_cap;
-        if (idx >= n) idx = n - 1;
-        g.bidx[probe] = idx;
-        double p = g.sum_tree[g.tree_cap + idx] / total;
-        double p_min = g.min_tree[1] / total;
-        double max_w = pow(p_min * (double)n, (double)-beta);
-        g.bw[probe] = (float)(pow(p * (double)n, (double)-beta) / max_w);
-        g.br[probe] = g.rr[idx];
-        g.bd[probe] = g.rd[idx];
-    }
-    idx = __shfl(idx, 0, 64);
-    // replay rows are random and never re-read — keep them out of L2
-    // (the weights need it; SURVEY hot-loop note)
-    for (int k = lane; k < g.O; k += 64) {
-        bs_out[(long)probe * g.O + k] =
-            __builtin_nontemporal_load(&g.rs[idx * g.O + k]);
-        g.bs2[(long)probe * g.O + k] =
-            __builtin_nontemporal_load(&g.rs2[idx * g.O + k]);
-    }
-    for (int k = lane; k < g.A; k += 64)
-        g.ba[(long)probe * g.A + k] =
-            __builtin_nontemporal_load(&g.ra[idx * g.A + k]);
+    per_sample_probe<true>(g, bs_out, probe, lane, epoch, beta_t);
 }
 
 // merged projection + CE-grad phase: the wave that projects row b's target
 // distribution keeps it in LDS and computes the CE gradient/priority
 // immediately (saves a barrier and the m_proj global round-trip; q comes
 // from PH4).  m_proj is still written out for introspection/parity tests.
-__device__ inline void p_project_ce(const PStepArgs& g, float* lds,
+__device__ inline void p_project_ce(const StepArgs& g, float* lds,
                                     int row_base = -1) {
     int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int row = (row_base < 0 ? (int)blockIdx.x * 4 : row_base) + wid;
+    if (row >= g.B) return;
     int K = g.K;
     float* mrow = lds + wid * 64;
-    for (int k = lane; k < K; k += 64) mrow[k] = 0.f;
-    __builtin_amdgcn_wave_barrier();
-    if (row < g.B && lane < K) {
-        float delta = (g.v_max - g.v_min) / (K - 1);
-        float z = g.v_min + lane * delta;
-        float tz = g.br[row] + g.gamma_n * (1.f - g.bd[row]) * z;
-        tz = fminf(g.v_max, fmaxf(g.v_min, tz));
-        int l, u;
-        float b = c51_bins(tz, g.v_min, delta, K, l, u);
-        float p = g.p_t[(long)row * K + lane];
-        atomicAdd(&mrow[l], p * ((float)u - b));
-        atomicAdd(&mrow[u], p * (b - (float)l));
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (row >= g.B) return;
+    float p = (lane < K) ? g.p_t[(long)row * K + lane] : 0.f;
+    c51_project_row(mrow, p, g.br[row], g.bd[row], g.v_min, g.v_max,
+                    g.gamma_n, K, lane);
     float qv = 0.f, mv = 0.f;
     if (lane < K) {
         g.m_proj[(long)row * K + lane] = mrow[lane];
         qv = g.q[(long)row * K + lane];
         mv = mrow[lane];
     }
-    float dot = mv * qv;
-    float ce = -mv * __logf(qv + 1e-10f);
-    for (int s = 32; s > 0; s >>= 1) {
-        dot += __shfl_xor(dot, s, 64);
-        ce += __shfl_xor(ce, s, 64);
-    }
     float scale = (g.is_weighting && g.bw) ? g.bw[row] : 1.f;
-    if (lane < K)
-        g.dlog[(long)row * K + lane] = scale * (qv - mv) / (float)g.B;
+    CeRow r = ce_grad_row(mv, qv, scale, g.B);
+    if (lane < K) g.dlog[(long)row * K + lane] = r.dz;
     if (lane == 0) {
-        g.pri[row] = dot + g.per_eps;
-        atomicAdd(&g.cnt->loss_critic, scale * ce / (float)g.B);
+        g.pri[row] = r.dot + g.per_eps;
+        atomicAdd(&g.cnt->loss_critic, scale * r.ce / (float)g.B);
     }
 }
 
 // narrow backward-dX (span <= 8, e.g. the concat action slice): one wave
 // per batch row, lane-parallel dot over `out` with a shfl reduce, tanh
 // mask applied from ymask.
-__device__ inline void p_bwd_dx_narrow(const PStepArgs& g, const float* dz,
+__device__ inline void p_bwd_dx_narrow(const StepArgs& g, const float* dz,
                                        const float* wt, int in_lo,
                                        int in_hi, int out,
                                        const float* ymask, float* dx,
@@ -724,66 +617,33 @@ __device__ inline void p_bwd_dx_narrow(const PStepArgs& g, const float* dz,
     }
 }
 
-__device__ inline void p_policy_grad(const PStepArgs& g,
+__device__ inline void p_policy_grad(const StepArgs& g,
                                      int row_base = -1) {
     int row = (row_base < 0 ? (int)blockIdx.x * 4 : row_base)
               + (threadIdx.x >> 6);
     int lane = threadIdx.x & 63;
     if (row >= g.B) return;
     int K = g.K;
-    float delta = (g.v_max - g.v_min) / (K - 1);
-    float z = g.v_min + lane * delta;
     float qv = (lane < K) ? g.pq[(long)row * K + lane] : 0.f;
-    float e = qv * z;
-    for (int s = 32; s > 0; s >>= 1) e += __shfl_xor(e, s, 64);
-    if (lane < K)
-        g.pd3[(long)row * K + lane] = -qv * (z - e) / (float)g.B;
+    float e;
+    float dz = policy_grad_row(qv, c51_atom(g.v_min, g.v_max, K, lane), g.B,
+                               e);
+    if (lane < K) g.pd3[(long)row * K + lane] = dz;
     if (lane == 0) atomicAdd(&g.cnt->loss_actor, -e / (float)g.B);
 }
 
-// PER write-back (k_per_update's tree repair without its counter tick —
-// k_step_persistent advances the counters once per launch); one workgroup,
-// `owner_wg`, does it
-__device__ inline void p_per_update(const PStepArgs& g, int owner_wg) {
+// PER write-back (k_per_update without its counter tick — k_step_persistent
+// advances the counters once per launch); one workgroup, `owner_wg`, does it
+__device__ inline void p_per_update(const StepArgs& g, int owner_wg) {
     if ((int)blockIdx.x != owner_wg) return;
-    int tid = threadIdx.x;
-    float local_max = 0.f;
-    for (int i = tid; i < g.B; i += 256) {
-        float p = g.pri[i];
-        double pa = pow((double)p, (double)g.per_alpha);
-        long leaf = g.tree_cap + g.bidx[i];
-        g.sum_tree[leaf] = pa;
-        g.min_tree[leaf] = pa;
-        local_max = fmaxf(local_max, p);
-    }
-    __shared__ float smax[256];
-    smax[tid] = local_max;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) smax[tid] = fmaxf(smax[tid], smax[tid + s]);
-        __syncthreads();
-    }
-    if (tid == 0)
-        g.cnt->max_priority = fmaxf(g.cnt->max_priority, smax[0]);
-    __syncthreads();
-    long levels = 0;
-    for (long c = g.tree_cap; c > 1; c >>= 1) ++levels;
-    for (long lv = 0; lv < levels; ++lv) {
-        for (int i = tid; i < g.B; i += 256) {
-            long node = (g.tree_cap + g.bidx[i]) >> (lv + 1);
-            if (node >= 1) {
-                g.sum_tree[node] =
-                    g.sum_tree[2 * node] + g.sum_tree[2 * node + 1];
-                g.min_tree[node] = fmin(g.min_tree[2 * node],
-                                        g.min_tree[2 * node + 1]);
-            }
-        }
-        __syncthreads();
-    }
+    per_write_leaves(g.sum_tree, g.min_tree, g.tree_cap, g.bidx, g.pri, g.B,
+                     g.per_alpha, g.cnt);
+    per_repair_paths(g.sum_tree, g.min_tree, g.tree_cap, g.B, 256,
+                     [&](int i) { return g.tree_cap + g.bidx[i]; });
 }
 
 __global__ void __launch_bounds__(256, 1)
-k_step_persistent(PStepArgs g, int nsteps) {
+k_step_persistent(StepArgs g, int nsteps) {
     __shared__ float lds[PLDS_FLOATS];
     unsigned long long tgt = g.gbar[160];   // cross-launch round base
     unsigned long long* ctr = g.gbar;

@@ -1,144 +1,42 @@
 // Replay and PER tree kernels: prioritized sampling + batch gather, priority
 // write-back (one-workgroup and grid-wide forms), ingestion, synthetic fill and
 // tree rebuild.  Used by the row-block and wide paths and by the host replay
-// ops; the persistent kernel carries its own p_sample / p_per_update.
+// ops.  The sampling, leaf-write and path-repair formulas themselves are the
+// engine_rowmath.hip helpers, which the persistent kernel's p_sample /
+// p_per_update call too.
 
 namespace d4pg {
 
 // ---- PER sample + gather ---------------------------------------------------
-// One wave per probe: lane 0 walks the sum tree (double, exact), all lanes
-// then cooperatively gather the transition row into the batch SoA.
-// Also computes IS weights w = ((p/total)*N)^-beta / max_w.
-__global__ void k_per_sample(
-        const double* __restrict__ sum_tree, const double* __restrict__ min_tree,
-        long tree_cap,
-        const float* __restrict__ rs, const float* __restrict__ ra,
-        const float* __restrict__ rr, const float* __restrict__ rs2,
-        const float* __restrict__ rd,
-        int obs, int act,
-        float* __restrict__ bs, float* __restrict__ ba, float* __restrict__ br,
-        float* __restrict__ bs2, float* __restrict__ bd,
-        float* __restrict__ bw, long* __restrict__ bidx,
-        int B, const Counters* __restrict__ cnt,
-        float beta0, float beta_iters, uint64_t seed) {
+// One wave per probe (per_sample_probe); first kernel of a row-block or wide
+// step, reading the schedule position from the device counters.
+__global__ void k_per_sample(StepArgs g) {
     int probe = blockIdx.x * (blockDim.x / 64) + (threadIdx.x / 64);
     int lane = threadIdx.x & 63;
-    if (probe >= B) return;
+    if (probe >= g.B) return;
     if (probe == 0 && lane == 0) {
         // first kernel of the step: reset the per-step loss accumulators
         // (counter increments happen in k_per_update at step end)
-        const_cast<Counters*>(cnt)->loss_critic = 0.f;
-        const_cast<Counters*>(cnt)->loss_actor = 0.f;
+        g.cnt->loss_critic = 0.f;
+        g.cnt->loss_actor = 0.f;
     }
-
-    long long n = cnt->size;
-    double total = sum_tree[1];
-    float frac = fminf((float)((double)cnt->beta_t / beta_iters), 1.0f);
-    float beta = beta0 + frac * (1.0f - beta0);
-
-    long idx;
-    if (lane == 0) {
-        Philox4 r = philox4(seed, (uint64_t)cnt->rng_epoch, (uint64_t)probe);
-        double mass = (double)u01(r.v[0]) * total;
-        long node = 1;
-        // 4-ary descent over the binary layout: a stored parent is
-        // bit-exactly the double-sum of its children, so comparing
-        // against grandchildren sums reproduces two binary steps with
-        // ONE contiguous 32 B load — half the dependent-load chain
-        // (20 levels -> 10 loads at 1e6 leaves).
-        while (node < tree_cap / 2) {
-            long gb = 4 * node;
-            double g0 = sum_tree[gb], g1 = sum_tree[gb + 1],
-                   g2 = sum_tree[gb + 2];
-            double s01 = g0 + g1;
-            if (mass <= s01) {
-                if (mass <= g0) node = gb;
-                else { mass -= g0; node = gb + 1; }
-            } else {
-                mass -= s01;
-                if (mass <= g2) node = gb + 2;
-                else { mass -= g2; node = gb + 3; }
-            }
-        }
-        if (node < tree_cap) {                 // odd final level
-            double ls = sum_tree[2 * node];
-            if (mass > ls) { mass -= ls; node = 2 * node + 1; }
-            else           { node = 2 * node; }
-        }
-        idx = node - tree_cap;
-        if (idx >= n) idx = n - 1;          // fp-roundoff guard at range top
-        bidx[probe] = idx;
-        // IS weight
-        double p = sum_tree[tree_cap + idx] / total;
-        double p_min = min_tree[1] / total;
-        double max_w = pow(p_min * (double)n, (double)-beta);
-        bw[probe] = (float)(pow(p * (double)n, (double)-beta) / max_w);
-        br[probe] = rr[idx];
-        bd[probe] = rd[idx];
-    }
-    idx = __shfl(idx, 0, 64);
-    for (int k = lane; k < obs; k += 64) {
-        bs[(long)probe * obs + k] = rs[idx * obs + k];
-        bs2[(long)probe * obs + k] = rs2[idx * obs + k];
-    }
-    for (int k = lane; k < act; k += 64)
-        ba[(long)probe * act + k] = ra[idx * act + k];
+    per_sample_probe<false>(g, g.bs, probe, lane, g.cnt->rng_epoch,
+                            g.cnt->beta_t);
 }
 
 // ---- PER priority write-back (K12 update path) ------------------------------
-// Exact level-synchronized tree repair: ONE workgroup; thread i owns probe i;
-// per level all touched parents are recomputed from their (already final)
-// children.  Duplicate parents write identical values (benign).
+// ONE workgroup of 256 threads: leaves, exact level-synchronized tree repair,
+// then the schedule tick — this is the last kernel of a row-block step.
 __global__ void k_per_update(double* __restrict__ sum_tree,
                              double* __restrict__ min_tree,
                              long tree_cap,
                              const long* __restrict__ idx,
                              const float* __restrict__ pri,
                              int B, float alpha, Counters* cnt) {
-    int tid = threadIdx.x;
-    // leaves
-    float local_max = 0.f;
-    for (int i = tid; i < B; i += blockDim.x) {
-        float p = pri[i];
-        double pa = pow((double)p, (double)alpha);
-        long leaf = tree_cap + idx[i];
-        sum_tree[leaf] = pa;
-        min_tree[leaf] = pa;
-        local_max = fmaxf(local_max, p);
-    }
-    // wg-reduce max priority
-    __shared__ float smax[256];
-    smax[tid] = local_max;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if (tid < s) smax[tid] = fmaxf(smax[tid], smax[tid + s]);
-        __syncthreads();
-    }
-    if (tid == 0)
-        cnt->max_priority = fmaxf(cnt->max_priority, smax[0]);
-    __syncthreads();
-    // level-synchronized repair
-    long levels = 0;
-    for (long c = tree_cap; c > 1; c >>= 1) ++levels;
-    for (long lv = 0; lv < levels; ++lv) {
-        for (int i = tid; i < B; i += blockDim.x) {
-            long node = (tree_cap + idx[i]) >> (lv + 1);
-            if (node >= 1) {
-                sum_tree[node] = sum_tree[2 * node] + sum_tree[2 * node + 1];
-                min_tree[node] = fmin(min_tree[2 * node],
-                                      min_tree[2 * node + 1]);
-            }
-        }
-        __syncthreads();
-    }
-    // last kernel of the step: advance the schedule counters for the NEXT
-    // step (counters are initialized to 1 so the first step sees t=1)
-    if (tid == 0) {
-        cnt->beta_t += 1;
-        cnt->adam_t_actor += 1;
-        cnt->adam_t_critic += 1;
-        cnt->rng_epoch += 1;
-    }
+    per_write_leaves(sum_tree, min_tree, tree_cap, idx, pri, B, alpha, cnt);
+    per_repair_paths(sum_tree, min_tree, tree_cap, B, 256,
+                     [&](int i) { return tree_cap + idx[i]; });
+    tick_counters(cnt);
 }
 
 // ---- PER write-back, wide-batch variant -------------------------------------
@@ -155,7 +53,7 @@ __global__ void k_per_leaves(double* __restrict__ sum_tree,
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < B;
          i += (long)gridDim.x * blockDim.x) {
         float p = pri[i];
-        double pa = pow((double)p, (double)alpha);
+        double pa = per_leaf_value(p, alpha);
         long leaf = tree_cap + idx[i];
         sum_tree[leaf] = pa;
         min_tree[leaf] = pa;
@@ -201,14 +99,7 @@ __global__ void k_per_level4(double* __restrict__ sum_tree,
     }
 }
 
-__global__ void k_tick_end(Counters* cnt) {
-    if (threadIdx.x == 0) {
-        cnt->beta_t += 1;
-        cnt->adam_t_actor += 1;
-        cnt->adam_t_critic += 1;
-        cnt->rng_epoch += 1;
-    }
-}
+__global__ void k_tick_end(Counters* cnt) { tick_counters(cnt); }
 
 // ---- replay ingestion (batched add) -----------------------------------------
 // T transitions appended at the ring position with priority max_priority^alpha,
@@ -228,7 +119,7 @@ __global__ void k_replay_add(float* __restrict__ rs, float* __restrict__ ra,
                              Counters* cnt) {
     int tid = threadIdx.x;
     long pos0 = cnt->pos;
-    double pa = pow((double)cnt->max_priority, (double)alpha);
+    double pa = per_leaf_value(cnt->max_priority, alpha);
     // copy rows (grid-stride inside the WG over T*max(obs,act) elems)
     for (long e = tid; e < (long)T * obs; e += blockDim.x) {
         long t = e / obs, k = e % obs;
@@ -249,20 +140,8 @@ __global__ void k_replay_add(float* __restrict__ rs, float* __restrict__ ra,
         min_tree[tree_cap + slot] = pa;
     }
     __syncthreads();
-    long levels = 0;
-    for (long c = tree_cap; c > 1; c >>= 1) ++levels;
-    for (long lv = 0; lv < levels; ++lv) {
-        for (int t = tid; t < T; t += blockDim.x) {
-            long slot = (pos0 + t) % capacity;
-            long node = (tree_cap + slot) >> (lv + 1);
-            if (node >= 1) {
-                sum_tree[node] = sum_tree[2 * node] + sum_tree[2 * node + 1];
-                min_tree[node] = fmin(min_tree[2 * node],
-                                      min_tree[2 * node + 1]);
-            }
-        }
-        __syncthreads();
-    }
+    per_repair_paths(sum_tree, min_tree, tree_cap, T, blockDim.x,
+                     [&](int t) { return tree_cap + (pos0 + t) % capacity; });
     if (tid == 0) {
         cnt->pos = (pos0 + T) % capacity;
         cnt->size = cnt->size + T > capacity ? capacity : cnt->size + T;

@@ -90,7 +90,7 @@ __global__ void k_roll_tick(RollArgs a, int tick, int slot, int emit_k,
                             int done) {
     long long ep = a.ep_state[0];
     long long base = a.ep_state[1];
-    double pa = pow((double)a.cnt->max_priority, (double)a.per_alpha);
+    double pa = per_leaf_value(a.cnt->max_priority, a.per_alpha);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.M;
          i += gridDim.x * blockDim.x) {
         // --- exploration noise (K11): per-env per-tick philox stream ---

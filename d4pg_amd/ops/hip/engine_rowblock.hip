@@ -79,13 +79,8 @@ __device__ inline void rb_fwd_softmax(const float* xb, float* qrow,
             a += xb[k] * wcol[(long)k * out];
         acc = a + bias[lane];
     }
-    float mx = acc;
-    for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-    float e = (lane < out) ? __expf(acc - mx) : 0.f;
-    float sum = e;
-    for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s, 64);
+    float q = softmax_wave(acc, lane < out);
     if (lane < out) {
-        float q = e / sum;
         qrow[lane] = q;
         if (grow) grow[lane] = q;
     }
@@ -112,30 +107,10 @@ __device__ inline void rb_bwd_dx(const float* dzb, const float* wt,
     }
 }
 
-// All geometry/pointers for the two row-block kernels.
-struct RowBlockArgs {
-    // dims
-    int B, O, A, H, K;
-    float v_min, v_max, gamma_n, per_eps;
-    int is_weighting;
-    // slabs
-    const float *p_actor, *p_actor_t, *p_critic, *p_critic_t;
-    LayerDesc al[4], cl[4];
-    // batch
-    const float *bs, *ba, *br, *bs2, *bd, *bw;
-    // outputs / saved activations
-    float *a2, *p_t, *m_proj, *q, *dlog, *pri;
-    float *c_h1, *c_h2, *c_h3, *d1, *d2, *d3;
-    float *pa_h1, *pa_h2, *pa_h3, *a_out;
-    float *pc_h1, *pc_h2, *pc_h3, *pq;
-    float *az1, *az2, *az3, *adz;
-    Counters* cnt;
-};
-
 // K2: target forwards + projection + critic forward + CE grad + priorities
 // + backward-dX chain.  One wave per row, no barriers.
 __global__ void __launch_bounds__(256)
-k_critic_rowblock(RowBlockArgs g) {
+k_critic_rowblock(StepArgs g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int b = blockIdx.x * 4 + wid;
@@ -164,23 +139,9 @@ k_critic_rowblock(RowBlockArgs g) {
                    g.p_t + (long)b * K, lane);          // r0 = p_t row
 
     // ---- C51 projection of r0 -> r1 (m row) ----
-    {
-        float delta = (g.v_max - g.v_min) / (K - 1);
-        float rr = g.br[b], dd = g.bd[b];
-        for (int k = lane; k < K; k += 64) L.r1[k] = 0.f;
-        if (lane < K) {
-            float z = g.v_min + lane * delta;
-            float tz = rr + g.gamma_n * (1.f - dd) * z;
-            tz = fminf(g.v_max, fmaxf(g.v_min, tz));
-            int l, u;
-            float bj = c51_bins(tz, g.v_min, delta, K, l, u);
-            float p = L.r0[lane];
-            atomicAdd(&L.r1[l], p * ((float)u - bj));
-            atomicAdd(&L.r1[u], p * (bj - (float)l));
-        }
-        for (int k = lane; k < K; k += 64)
-            g.m_proj[(long)b * K + k] = L.r1[k];
-    }
+    c51_project_row(L.r1, (lane < K) ? L.r0[lane] : 0.f, g.br[b], g.bd[b],
+                    g.v_min, g.v_max, g.gamma_n, K, lane);
+    if (lane < K) g.m_proj[(long)b * K + lane] = L.r1[lane];
 
     // ---- critic(s, a) -> q (saving h1..h3) ----
     for (int k = lane; k < O; k += 64) L.xb[k] = g.bs[(long)b * O + k];
@@ -198,21 +159,15 @@ k_critic_rowblock(RowBlockArgs g) {
     {
         float qv = (lane < K) ? L.r0[lane] : 0.f;
         float mv = (lane < K) ? L.r1[lane] : 0.f;
-        float dot = mv * qv;
-        float ce = -mv * __logf(qv + 1e-10f);
-        for (int s = 32; s > 0; s >>= 1) {
-            dot += __shfl_xor(dot, s, 64);
-            ce += __shfl_xor(ce, s, 64);
-        }
         float scale = (g.is_weighting && g.bw) ? g.bw[b] : 1.f;
+        CeRow r = ce_grad_row(mv, qv, scale, g.B);
         if (lane < K) {
-            float dz = scale * (qv - mv) / (float)g.B;
-            L.r2[lane] = dz;
-            g.dlog[(long)b * K + lane] = dz;
+            L.r2[lane] = r.dz;
+            g.dlog[(long)b * K + lane] = r.dz;
         }
         if (lane == 0) {
-            g.pri[b] = dot + g.per_eps;
-            atomicAdd(&g.cnt->loss_critic, scale * ce / (float)g.B);
+            g.pri[b] = r.dot + g.per_eps;
+            atomicAdd(&g.cnt->loss_critic, scale * r.ce / (float)g.B);
         }
     }
 
@@ -228,7 +183,7 @@ k_critic_rowblock(RowBlockArgs g) {
 // K5: actor forward + critic(s, actor(s)) + policy grad + dX chain down to
 // the actor's per-layer dz's.  One wave per row.
 __global__ void __launch_bounds__(256)
-k_policy_rowblock(RowBlockArgs g) {
+k_policy_rowblock(StepArgs g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int b = blockIdx.x * 4 + wid;
@@ -263,12 +218,11 @@ k_policy_rowblock(RowBlockArgs g) {
 
     // ---- policy head gradient: pd4 = -q (z - E[z]) / B ----
     {
-        float delta = (g.v_max - g.v_min) / (K - 1);
-        float z = g.v_min + lane * delta;
         float qv = (lane < K) ? L.r0[lane] : 0.f;
-        float e = qv * z;
-        for (int s = 32; s > 0; s >>= 1) e += __shfl_xor(e, s, 64);
-        if (lane < K) L.r2[lane] = -qv * (z - e) / (float)g.B;
+        float e;
+        float dz = policy_grad_row(qv, c51_atom(g.v_min, g.v_max, K, lane),
+                                   g.B, e);
+        if (lane < K) L.r2[lane] = dz;
         if (lane == 0) atomicAdd(&g.cnt->loss_actor, -e / (float)g.B);
     }
 

@@ -1,0 +1,272 @@
+// Row and probe formulas of the train step, one device implementation each:
+// the wave-wide softmax, the C51 projection scatter, the CE and policy-head
+// gradients, the PER descent / IS weight / sample+gather, the leaf write and
+// level-synchronised path repair of the sum/min trees, the schedule-counter
+// tick and Adam's bias-correction terms.  Used by all three paths
+// (persistent, row-block, wide) and by the replay kernels, which is what keeps
+// them bit-for-bit equal.  A "row" helper is called by one whole wave (64
+// lanes, lane = atom); a "workgroup-wide" helper by every thread of the
+// workgroup.  Helpers take plain values and pointers (the sample body, which
+// touches twenty buffers, takes the StepArgs) and fix the operation order;
+// callers own tiling, launch geometry and loss accumulation.
+
+namespace d4pg {
+
+// softmax over the valid lanes of a wave: lane's e / sum (0 on invalid lanes).
+// (p_fwd keeps its own spelling of this, see the note there.)
+__device__ __forceinline__ float softmax_wave(float v, bool valid) {
+    float mx = valid ? v : -INFINITY;
+    for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+    float e = valid ? __expf(v - mx) : 0.f;
+    float sum = e;
+    for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s, 64);
+    return e / sum;
+}
+
+// ---- C51 -------------------------------------------------------------------
+// Fractional bin position b of a clamped Tz and its two neighbour bins l < u.
+// In float32 (v_max - v_min) / delta can round ABOVE K-1 (e.g. 27.000002 at
+// K=28 on [-300, 0]); uncapped, ceil(b) = K indexes one float past the row.
+// Capping b at K-1 leaves every in-range value bit-identical.  Equal-bin
+// handling as in algo/projection.py (index-adjust so weights become (0,1)).
+__device__ __forceinline__ float c51_bins(float tz, float v_min, float delta,
+                                          int K, int& l, int& u) {
+    float b = fminf((tz - v_min) / delta, (float)(K - 1));
+    l = (int)floorf(b);
+    u = (int)ceilf(b);
+    if (l == u) { if (u > 0) l -= 1; else u += 1; }
+    return b;
+}
+
+// atom `lane` of the support
+__device__ __forceinline__ float c51_atom(float v_min, float v_max, int K,
+                                          int lane) {
+    float delta = (v_max - v_min) / (K - 1);
+    return v_min + lane * delta;
+}
+
+// Project one row's target distribution (lane's p = p_t[row][lane]) through
+// Tz = r + gamma_n (1 - d) z into the wave-private LDS row mrow[64]; on
+// return mrow[0..K) holds the projected row m.
+__device__ __forceinline__ void c51_project_row(float* mrow, float p, float r,
+                                                float d, float v_min,
+                                                float v_max, float gamma_n,
+                                                int K, int lane) {
+    mrow[lane] = 0.f;
+    __builtin_amdgcn_wave_barrier();
+    if (lane < K) {
+        float delta = (v_max - v_min) / (K - 1);
+        float z = v_min + lane * delta;
+        float tz = r + gamma_n * (1.f - d) * z;
+        tz = fminf(v_max, fmaxf(v_min, tz));
+        int l, u;
+        float b = c51_bins(tz, v_min, delta, K, l, u);
+        atomicAdd(&mrow[l], p * ((float)u - b));
+        atomicAdd(&mrow[u], p * (b - (float)l));
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// CE gradient of one row (mv, qv are 0 on lanes >= K): lane's dlogit, and
+// wave-reduced on every lane dot = <m, q> (the priority before per_eps) and
+// ce = -<m, log q> (the row's loss before scale / B).
+struct CeRow { float dz, dot, ce; };
+
+__device__ __forceinline__ CeRow ce_grad_row(float mv, float qv, float scale,
+                                             int B) {
+    float dot = mv * qv;
+    float ce = -mv * __logf(qv + 1e-10f);
+    for (int s = 32; s > 0; s >>= 1) {
+        dot += __shfl_xor(dot, s, 64);
+        ce += __shfl_xor(ce, s, 64);
+    }
+    return {scale * (qv - mv) / (float)B, dot, ce};
+}
+
+// Policy-head gradient of one row through the softmax:
+// L = -(1/B) sum_b sum_k q_k z_k  =>  dlogits_j = -q_j (z_j - E_q[z]) / B.
+// e returns E_q[z], wave-reduced (the row's loss is -e / B).
+__device__ __forceinline__ float policy_grad_row(float qv, float z, int B,
+                                                 float& e) {
+    e = qv * z;
+    for (int s = 32; s > 0; s >>= 1) e += __shfl_xor(e, s, 64);
+    return -qv * (z - e) / (float)B;
+}
+
+// ---- PER sampling ----------------------------------------------------------
+// 4-ary descent over the binary layout: a stored parent is bit-exactly the
+// double-sum of its children, so comparing against grandchildren sums
+// reproduces two binary steps with ONE contiguous 32 B load — half the
+// dependent-load chain (20 levels -> 10 loads at 1e6 leaves).  NT: deep levels
+// are random-access and read once per step, so they bypass L2 and leave the
+// hot top of the tree cached.  Returns the leaf NODE (leaf index + tree_cap).
+template <bool NT>
+__device__ __forceinline__ long per_descend(const double* sum_tree,
+                                            long tree_cap, double mass) {
+    auto ld = [&](long i, bool deep) {
+        return (NT && deep) ? __builtin_nontemporal_load(&sum_tree[i])
+                            : sum_tree[i];
+    };
+    long node = 1;
+    while (node < tree_cap / 2) {
+        long gb = 4 * node;
+        bool deep = gb >= 16384;
+        double g0 = ld(gb, deep), g1 = ld(gb + 1, deep),
+               g2 = ld(gb + 2, deep);
+        double s01 = g0 + g1;
+        if (mass <= s01) {
+            if (mass <= g0) node = gb;
+            else { mass -= g0; node = gb + 1; }
+        } else {
+            mass -= s01;
+            if (mass <= g2) node = gb + 2;
+            else { mass -= g2; node = gb + 3; }
+        }
+    }
+    if (node < tree_cap) {                 // odd final level
+        double ls = ld(2 * node, node >= 16384);
+        if (mass > ls) { mass -= ls; node = 2 * node + 1; }
+        else           { node = 2 * node; }
+    }
+    return node;
+}
+
+// beta of the linear schedule at position beta_t
+__device__ __forceinline__ float per_beta(long long beta_t, float beta0,
+                                          float beta_iters) {
+    float frac = fminf((float)((double)beta_t / beta_iters), 1.0f);
+    return beta0 + frac * (1.0f - beta0);
+}
+
+// IS weight w = (p N)^-beta / max_w, max_w from the smallest priority
+__device__ __forceinline__ float per_is_weight(double p, double p_min,
+                                               long long n, float beta) {
+    double max_w = pow(p_min * (double)n, (double)-beta);
+    return (float)(pow(p * (double)n, (double)-beta) / max_w);
+}
+
+// PER sample + gather of one probe by one wave: lane 0 walks the sum tree
+// (double, exact) and writes the IS weight, all lanes then cooperatively
+// gather the transition row into the batch SoA, states into bs_out.  epoch /
+// beta_t are the schedule values of the step being sampled.  NT also keeps
+// the gathered replay rows (random, never re-read) out of L2.
+template <bool NT>
+__device__ __forceinline__ void per_sample_probe(const StepArgs& g,
+                                                 float* bs_out, int probe,
+                                                 int lane, long long epoch,
+                                                 long long beta_t) {
+    auto ld = [](const float* p) {
+        return NT ? __builtin_nontemporal_load(p) : *p;
+    };
+    long long n = g.cnt->size;
+    double total = g.sum_tree[1];
+    float beta = per_beta(beta_t, g.per_beta0, g.per_beta_iters);
+    long idx;
+    if (lane == 0) {
+        Philox4 r = philox4(g.seed, (uint64_t)epoch, (uint64_t)probe);
+        double mass = (double)u01(r.v[0]) * total;
+        idx = per_descend<NT>(g.sum_tree, g.tree_cap, mass) - g.tree_cap;
+        if (idx >= n) idx = n - 1;          // fp-roundoff guard at range top
+        g.bidx[probe] = idx;
+        g.bw[probe] = per_is_weight(g.sum_tree[g.tree_cap + idx] / total,
+                                    g.min_tree[1] / total, n, beta);
+        g.br[probe] = g.rr[idx];
+        g.bd[probe] = g.rd[idx];
+    }
+    idx = __shfl(idx, 0, 64);
+    for (int k = lane; k < g.O; k += 64) {
+        bs_out[(long)probe * g.O + k] = ld(&g.rs[idx * g.O + k]);
+        g.bs2[(long)probe * g.O + k] = ld(&g.rs2[idx * g.O + k]);
+    }
+    for (int k = lane; k < g.A; k += 64)
+        g.ba[(long)probe * g.A + k] = ld(&g.ra[idx * g.A + k]);
+}
+
+// ---- PER write-back --------------------------------------------------------
+// leaf value of a priority
+__device__ __forceinline__ double per_leaf_value(float p, float alpha) {
+    return pow((double)p, (double)alpha);
+}
+
+// Workgroup-wide (256 threads): write the B sampled leaves from pri and fold
+// their largest priority into cnt->max_priority.  Ends on a barrier.
+__device__ __forceinline__ void per_write_leaves(double* sum_tree,
+                                                 double* min_tree,
+                                                 long tree_cap,
+                                                 const long* idx,
+                                                 const float* pri, int B,
+                                                 float alpha, Counters* cnt) {
+    int tid = threadIdx.x;
+    float local_max = 0.f;
+    for (int i = tid; i < B; i += 256) {
+        float p = pri[i];
+        double pa = per_leaf_value(p, alpha);
+        long leaf = tree_cap + idx[i];
+        sum_tree[leaf] = pa;
+        min_tree[leaf] = pa;
+        local_max = fmaxf(local_max, p);
+    }
+    __shared__ float smax[256];
+    smax[tid] = local_max;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) smax[tid] = fmaxf(smax[tid], smax[tid + s]);
+        __syncthreads();
+    }
+    if (tid == 0)
+        cnt->max_priority = fmaxf(cnt->max_priority, smax[0]);
+    __syncthreads();
+}
+
+// Workgroup-wide exact level-synchronised repair of the paths above n
+// already-written leaves (leaf_of(i) = leaf NODE of item i): per level all
+// touched parents are recomputed from their (already final) children.
+// Duplicate parents write identical values (benign).  nthr = workgroup size.
+template <typename LeafOf>
+__device__ __forceinline__ void per_repair_paths(double* sum_tree,
+                                                 double* min_tree,
+                                                 long tree_cap, int n,
+                                                 int nthr, LeafOf leaf_of) {
+    long levels = 0;
+    for (long c = tree_cap; c > 1; c >>= 1) ++levels;
+    for (long lv = 0; lv < levels; ++lv) {
+        for (int i = threadIdx.x; i < n; i += nthr) {
+            long node = leaf_of(i) >> (lv + 1);
+            if (node >= 1) {
+                sum_tree[node] = sum_tree[2 * node] + sum_tree[2 * node + 1];
+                min_tree[node] = fmin(min_tree[2 * node],
+                                      min_tree[2 * node + 1]);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Advance the schedule counters for the NEXT step (they are initialised to 1
+// so the first step sees t=1); thread 0 of the step's last kernel.
+__device__ __forceinline__ void tick_counters(Counters* cnt) {
+    if (threadIdx.x == 0) {
+        cnt->beta_t += 1;
+        cnt->adam_t_actor += 1;
+        cnt->adam_t_critic += 1;
+        cnt->rng_epoch += 1;
+    }
+}
+
+// ---- Adam ----------------------------------------------------------------
+// The bias-correction terms 1 - beta^t at step t.  Only these are shared: the
+// element update itself stays written out in k_adam_lerp and p_adam_lerp.
+// Device code is built with fp-contract=fast, and the compiler already rounds
+// the two differently (k_adam_lerp multiplies then adds for both moments,
+// p_adam_lerp fuses the second moment into an fma); one inline helper made
+// the persistent kernel fuse the first moment too and changed its parameters
+// in the last bit.  Sharing it needs explicit fmaf and a deliberate change
+// of one path's results.
+struct AdamBias { float bc1, bc2; };
+
+__device__ __forceinline__ AdamBias adam_bias(float b1, float b2,
+                                              long long t) {
+    return {1.f - __powf(b1, (float)t), 1.f - __powf(b2, (float)t)};
+}
+
+}  // namespace d4pg

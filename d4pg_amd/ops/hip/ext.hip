@@ -48,7 +48,7 @@ static py::dict info(int64_t h) {
     py::dict d;
     d["n_params_actor"] = e.anet.n_params;
     d["n_params_critic"] = e.cnet.n_params;
-    d["tree_cap"] = e.tree_cap;
+    d["tree_cap"] = e.ws.tree_cap;
     d["persistent"] = e.step_path() == Engine::PATH_PERSISTENT;
     d["seed"] = (int64_t)e.cfg.seed;
     py::list al, cl;
@@ -76,16 +76,16 @@ static torch::Tensor f32_contig(torch::Tensor t) {
 // which: 0 actor, 1 actor_target, 2 critic, 3 critic_target
 static float* slab_ptr(Engine& e, int64_t which, long& n) {
     switch (which) {
-        case 0: n = e.anet.n_params; return e.p_actor;
-        case 1: n = e.anet.n_params; return e.p_actor_t;
-        case 2: n = e.cnet.n_params; return e.p_critic;
-        case 3: n = e.cnet.n_params; return e.p_critic_t;
-        case 4: n = e.anet.n_params; return e.g_actor;
-        case 5: n = e.cnet.n_params; return e.g_critic;
-        case 6: n = e.anet.n_params; return e.m_actor;
-        case 7: n = e.anet.n_params; return e.v_actor;
-        case 8: n = e.cnet.n_params; return e.m_critic;
-        case 9: n = e.cnet.n_params; return e.v_critic;
+        case 0: n = e.anet.n_params; return e.ws.p_actor;
+        case 1: n = e.anet.n_params; return e.ws.p_actor_t;
+        case 2: n = e.cnet.n_params; return e.ws.p_critic;
+        case 3: n = e.cnet.n_params; return e.ws.p_critic_t;
+        case 4: n = e.anet.n_params; return e.ws.g_actor;
+        case 5: n = e.cnet.n_params; return e.ws.g_critic;
+        case 6: n = e.anet.n_params; return e.ws.m_actor;
+        case 7: n = e.anet.n_params; return e.ws.v_actor;
+        case 8: n = e.cnet.n_params; return e.ws.m_critic;
+        case 9: n = e.cnet.n_params; return e.ws.v_critic;
     }
     throw std::runtime_error("bad slab id");
 }
@@ -129,7 +129,7 @@ static void ingest(int64_t h, torch::Tensor s, torch::Tensor a,
 // the same convention Engine::alloc establishes at step 0)
 static void set_seed(int64_t h, int64_t seed) {
     Engine& e = get(h);
-    e.cfg.seed = (uint64_t)seed;
+    e.cfg.seed = e.ws.seed = (uint64_t)seed;
     // the seed is baked into captured kernel ARGUMENTS (k_per_sample /
     // k_step_persistent take it by value), so a previously captured
     // hipGraph would silently keep sampling with the stale seed —
@@ -141,18 +141,18 @@ static void set_seed(int64_t h, int64_t seed) {
 static void set_schedule(int64_t h, int64_t steps_done, double max_priority) {
     Engine& e = get(h);
     Counters c{};
-    HIP_CHECK(hipMemcpy(&c, e.cnt, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&c, e.ws.cnt, sizeof(c), hipMemcpyDeviceToHost));
     c.beta_t = steps_done;
     c.adam_t_actor = c.adam_t_critic = c.rng_epoch = steps_done + 1;
     c.max_priority = (float)max_priority;
-    HIP_CHECK(hipMemcpy(e.cnt, &c, sizeof(c), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(e.ws.cnt, &c, sizeof(c), hipMemcpyHostToDevice));
 }
 
 // on-HBM replay snapshot: SoA rows [0, size) + both segment trees
 static py::dict replay_state(int64_t h) {
     Engine& e = get(h);
     Counters c{};
-    HIP_CHECK(hipMemcpy(&c, e.cnt, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&c, e.ws.cnt, sizeof(c), hipMemcpyDeviceToHost));
     long n = c.size;
     const int O = e.cfg.obs, A = e.cfg.act;
     py::dict d;
@@ -163,17 +163,17 @@ static py::dict replay_state(int64_t h) {
                                 hipMemcpyDeviceToHost));
         return t;
     };
-    d["s"] = grab(e.rs, n, O);
-    d["a"] = grab(e.ra, n, A);
-    d["r"] = grab(e.rr, n, 1);
-    d["s2"] = grab(e.rs2, n, O);
-    d["d"] = grab(e.rd, n, 1);
-    auto st = torch::empty({2 * e.tree_cap}, torch::kFloat64);
-    auto mt = torch::empty({2 * e.tree_cap}, torch::kFloat64);
-    HIP_CHECK(hipMemcpy(st.data_ptr<double>(), e.sum_tree,
-                        2 * e.tree_cap * 8, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(mt.data_ptr<double>(), e.min_tree,
-                        2 * e.tree_cap * 8, hipMemcpyDeviceToHost));
+    d["s"] = grab(e.ws.rs, n, O);
+    d["a"] = grab(e.ws.ra, n, A);
+    d["r"] = grab(e.ws.rr, n, 1);
+    d["s2"] = grab(e.ws.rs2, n, O);
+    d["d"] = grab(e.ws.rd, n, 1);
+    auto st = torch::empty({2 * e.ws.tree_cap}, torch::kFloat64);
+    auto mt = torch::empty({2 * e.ws.tree_cap}, torch::kFloat64);
+    HIP_CHECK(hipMemcpy(st.data_ptr<double>(), e.ws.sum_tree,
+                        2 * e.ws.tree_cap * 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(mt.data_ptr<double>(), e.ws.min_tree,
+                        2 * e.ws.tree_cap * 8, hipMemcpyDeviceToHost));
     d["sum_tree"] = st;
     d["min_tree"] = mt;
     d["size"] = c.size;
@@ -190,7 +190,7 @@ static void load_replay_state(int64_t h, torch::Tensor s, torch::Tensor a,
     Engine& e = get(h);
     const int O = e.cfg.obs, A = e.cfg.act;
     long n = size;
-    TORCH_CHECK(sum_tree.numel() == 2 * e.tree_cap, "tree size mismatch");
+    TORCH_CHECK(sum_tree.numel() == 2 * e.ws.tree_cap, "tree size mismatch");
     auto put = [&](float* dst, torch::Tensor t, long rows, long w) {
         auto tt = f32_contig(t);
         TORCH_CHECK(tt.numel() == rows * w, "replay slab size mismatch");
@@ -198,23 +198,23 @@ static void load_replay_state(int64_t h, torch::Tensor s, torch::Tensor a,
             HIP_CHECK(hipMemcpy(dst, tt.data_ptr<float>(), rows * w * 4,
                                 hipMemcpyHostToDevice));
     };
-    put(e.rs, s, n, O);
-    put(e.ra, a, n, A);
-    put(e.rr, r, n, 1);
-    put(e.rs2, s2, n, O);
-    put(e.rd, dn, n, 1);
+    put(e.ws.rs, s, n, O);
+    put(e.ws.ra, a, n, A);
+    put(e.ws.rr, r, n, 1);
+    put(e.ws.rs2, s2, n, O);
+    put(e.ws.rd, dn, n, 1);
     auto st = sum_tree.to(torch::kFloat64).contiguous().cpu();
     auto mt = min_tree.to(torch::kFloat64).contiguous().cpu();
-    HIP_CHECK(hipMemcpy(e.sum_tree, st.data_ptr<double>(),
-                        2 * e.tree_cap * 8, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(e.min_tree, mt.data_ptr<double>(),
-                        2 * e.tree_cap * 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(e.ws.sum_tree, st.data_ptr<double>(),
+                        2 * e.ws.tree_cap * 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(e.ws.min_tree, mt.data_ptr<double>(),
+                        2 * e.ws.tree_cap * 8, hipMemcpyHostToDevice));
     Counters c{};
-    HIP_CHECK(hipMemcpy(&c, e.cnt, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&c, e.ws.cnt, sizeof(c), hipMemcpyDeviceToHost));
     c.size = size;
     c.pos = pos;
     c.max_priority = (float)max_priority;
-    HIP_CHECK(hipMemcpy(e.cnt, &c, sizeof(c), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(e.ws.cnt, &c, sizeof(c), hipMemcpyHostToDevice));
 }
 
 static void step(int64_t h, int64_t n) { get(h).step((int)n); }
@@ -316,29 +316,29 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
     }
     struct Ent { const void* p; std::vector<long> shape; bool is_long; bool is_double; };
     std::unordered_map<std::string, Ent> m = {
-        {"bs", {e.bs, {B, O}, false, false}},
-        {"bs_b", {e.bs_b, {B, O}, false, false}},
-        {"ba", {e.ba, {B, A}, false, false}},
-        {"br", {e.br, {B}, false, false}},
-        {"bs2", {e.bs2, {B, O}, false, false}},
-        {"bd", {e.bd, {B}, false, false}},
-        {"bw", {e.bw, {B}, false, false}},
-        {"pri", {e.pri, {B}, false, false}},
-        {"bidx", {e.bidx, {B}, true, false}},
-        {"a2", {e.a2, {B, A}, false, false}},
-        {"p_t", {e.p_t, {B, K}, false, false}},
-        {"m_proj", {e.m_proj, {B, K}, false, false}},
-        {"q", {e.q, {B, K}, false, false}},
-        {"pq", {e.pq, {B, K}, false, false}},
-        {"a_out", {e.a_out, {B, A}, false, false}},
-        {"dlog", {e.dlog, {B, K}, false, false}},
-        {"c_h1", {e.c_h1, {B, H}, false, false}},
-        {"c_h2", {e.c_h2, {B, H}, false, false}},
-        {"c_h3", {e.c_h3, {B, H}, false, false}},
-        {"at_h1", {e.at_h1, {B, H}, false, false}},
-        {"tstamp", {e.tstamp, {64}, true, false}},
-        {"sum_tree", {e.sum_tree, {2 * e.tree_cap}, false, true}},
-        {"min_tree", {e.min_tree, {2 * e.tree_cap}, false, true}},
+        {"bs", {e.ws.bs, {B, O}, false, false}},
+        {"bs_b", {e.ws.bs_b, {B, O}, false, false}},
+        {"ba", {e.ws.ba, {B, A}, false, false}},
+        {"br", {e.ws.br, {B}, false, false}},
+        {"bs2", {e.ws.bs2, {B, O}, false, false}},
+        {"bd", {e.ws.bd, {B}, false, false}},
+        {"bw", {e.ws.bw, {B}, false, false}},
+        {"pri", {e.ws.pri, {B}, false, false}},
+        {"bidx", {e.ws.bidx, {B}, true, false}},
+        {"a2", {e.ws.a2, {B, A}, false, false}},
+        {"p_t", {e.ws.p_t, {B, K}, false, false}},
+        {"m_proj", {e.ws.m_proj, {B, K}, false, false}},
+        {"q", {e.ws.q, {B, K}, false, false}},
+        {"pq", {e.ws.pq, {B, K}, false, false}},
+        {"a_out", {e.ws.a_out, {B, A}, false, false}},
+        {"dlog", {e.ws.dlog, {B, K}, false, false}},
+        {"c_h1", {e.ws.c_h1, {B, H}, false, false}},
+        {"c_h2", {e.ws.c_h2, {B, H}, false, false}},
+        {"c_h3", {e.ws.c_h3, {B, H}, false, false}},
+        {"at_h1", {e.ws.at_h1, {B, H}, false, false}},
+        {"tstamp", {e.ws.tstamp, {64}, true, false}},
+        {"sum_tree", {e.ws.sum_tree, {2 * e.ws.tree_cap}, false, true}},
+        {"min_tree", {e.ws.min_tree, {2 * e.ws.tree_cap}, false, true}},
     };
     auto it = m.find(name);
     if (it == m.end()) throw std::runtime_error("unknown buffer " + name);
