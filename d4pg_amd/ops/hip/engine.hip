@@ -728,6 +728,15 @@ public:
                 const float* hs2, const float* hd, int T) {
         if (T > ing_cap) throw std::runtime_error("ingest batch too large");
         const int O = cfg.obs, A = cfg.act;
+        // One call longer than the ring: rows t and t + capacity share a
+        // slot, and the kernels' unordered threads would leave it holding
+        // parts of both.  Only the last `capacity` rows survive anyway, so
+        // drop the leading ones and start `skip` slots further on; pos
+        // still ends at (pos + T) % capacity.
+        const long skip = T > cfg.capacity ? T - cfg.capacity : 0;
+        hs += skip * O; ha += skip * A; hr += skip;
+        hs2 += skip * O; hd += skip;
+        T -= (int)skip;
         HIP_CHECK(hipMemcpyAsync(ing_s, hs, (long)T * O * 4,
                                  hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipMemcpyAsync(ing_a, ha, (long)T * A * 4,
@@ -743,7 +752,8 @@ public:
                                ws.rs, ws.ra, ws.rr, ws.rs2, ws.rd,
                                ws.sum_tree, ws.min_tree, ws.tree_cap,
                                cfg.capacity, ing_s, ing_a, ing_r,
-                               ing_s2, ing_d, T, O, A, cfg.per_alpha, ws.cnt);
+                               ing_s2, ing_d, T, O, A, cfg.per_alpha, skip,
+                               ws.cnt);
         } else {
             // bulk path: grid-wide copy + leaf init, then a full
             // bandwidth-bound tree rebuild (far cheaper than one wg
@@ -756,14 +766,14 @@ public:
             hipLaunchKernelGGL(k_replay_copy, dim3(1024), dim3(256), 0,
                                stream, ws.rs, ws.ra, ws.rr, ws.rs2, ws.rd,
                                ws.sum_tree, ws.min_tree, ws.tree_cap,
-                               cfg.capacity, h.pos,
+                               cfg.capacity, (h.pos + skip) % cfg.capacity,
                                ing_s, ing_a, ing_r, ing_s2, ing_d, T, O, A,
                                pa);
             for (long lo = ws.tree_cap / 2; lo >= 1; lo >>= 1)
                 hipLaunchKernelGGL(k_tree_build_level, dim3(1024),
                                    dim3(256), 0, stream, ws.sum_tree,
                                    ws.min_tree, lo, 2 * lo);
-            h.pos = (h.pos + T) % cfg.capacity;
+            h.pos = (h.pos + skip + T) % cfg.capacity;
             h.size = h.size + T > cfg.capacity ? cfg.capacity : h.size + T;
             HIP_CHECK(hipMemcpyAsync(ws.cnt, &h, sizeof(h),
                                      hipMemcpyHostToDevice, stream));
@@ -935,7 +945,10 @@ public:
         }
         HIP_CHECK(hipMemcpy(roll_.obs, obs.data(), 3L * M * 4,
                             hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(roll_.ou_x, 0, M * 4));
+        // as k_roll_reset leaves it: the OU process starts at mu
+        std::vector<float> ou(M, roll_.ou_mu);
+        HIP_CHECK(hipMemcpy(roll_.ou_x, ou.data(), M * 4,
+                            hipMemcpyHostToDevice));
     }
 
     // actor forward for eval/smoke: x[B,obs] (device via staging) -> a[B,act]

@@ -116,9 +116,10 @@ __global__ void k_replay_add(float* __restrict__ rs, float* __restrict__ ra,
                              const float* __restrict__ ts2,
                              const float* __restrict__ td,
                              int T, int obs, int act, float alpha,
-                             Counters* cnt) {
+                             long skip, Counters* cnt) {
     int tid = threadIdx.x;
-    long pos0 = cnt->pos;
+    // skip: rows the host dropped from a call longer than the ring
+    long pos0 = (cnt->pos + skip) % capacity;
     double pa = per_leaf_value(cnt->max_priority, alpha);
     // copy rows (grid-stride inside the WG over T*max(obs,act) elems)
     for (long e = tid; e < (long)T * obs; e += blockDim.x) {

@@ -1,5 +1,6 @@
-"""Plain numpy oracles for the fused engine's PER sampling and C51
-projection (shared by the CPU and GPU tests; not a conftest).
+"""Plain numpy oracles for the fused engine's PER sampling, C51 projection,
+replay ring and rollout noise streams (shared by the CPU and GPU tests; not a
+conftest).
 
 Everything here is written for clarity, not speed: python loops, float64
 mass arithmetic.  Where the engine's result depends on a float32 rounding
@@ -140,6 +141,78 @@ def project64(p, r, d, v_min, v_max, gamma_n):
                 m[i, lo] += p[i, j] * (hi - float(b))
                 m[i, hi] += p[i, j] * (float(b) - lo)
     return m
+
+
+# ---------------------------------------------------------------------------
+# replay write side: the ring, and the rollout's philox streams
+# ---------------------------------------------------------------------------
+
+class RingOracle:
+    """The on-HBM replay as a plain numpy ring: rows are written one at a
+    time at `pos`, so on a duplicate slot the last write wins; each new row's
+    tree leaf is `leaf` (float64)."""
+
+    def __init__(self, capacity, tree_cap):
+        assert capacity <= tree_cap
+        self.capacity, self.tree_cap = int(capacity), int(tree_cap)
+        self.size = self.pos = 0
+        self.rows = None
+        self.leaves = np.zeros(self.capacity, np.float64)
+
+    def add(self, s, a, r, s2, d, leaf=1.0):
+        s, a, s2 = (np.asarray(x, np.float32) for x in (s, a, s2))
+        r = np.asarray(r, np.float32).ravel()
+        d = np.asarray(d, np.float32).ravel()
+        T = len(r)
+        s, a, s2 = s.reshape(T, -1), a.reshape(T, -1), s2.reshape(T, -1)
+        if self.rows is None:
+            c = self.capacity
+            self.rows = dict(s=np.zeros((c, s.shape[1]), np.float32),
+                             a=np.zeros((c, a.shape[1]), np.float32),
+                             r=np.zeros(c, np.float32),
+                             s2=np.zeros((c, s.shape[1]), np.float32),
+                             d=np.zeros(c, np.float32))
+        for t in range(T):
+            i = self.pos
+            self.rows["s"][i], self.rows["a"][i] = s[t], a[t]
+            self.rows["r"][i], self.rows["d"][i] = r[t], d[t]
+            self.rows["s2"][i] = s2[t]
+            self.leaves[i] = leaf
+            self.pos = (i + 1) % self.capacity
+            self.size = min(self.size + 1, self.capacity)
+
+    def occupied(self):
+        """(s, a, r, s2, d) over rows [0, size)."""
+        return tuple(self.rows[k][:self.size]
+                     for k in ("s", "a", "r", "s2", "d"))
+
+    def trees(self):
+        return build_trees(self.leaves[:self.size], self.tree_cap)
+
+
+def n01(a, b):
+    """The rollout kernel's Box-Muller on two philox words: the uniforms are
+    the kernel's float32 u01, the transcendental part is float64."""
+    u1 = max(float(u01(a)), 1e-12)
+    u2 = float(u01(b))
+    return float(np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2))
+
+
+def roll_noise_words(seed, ep, tick, env):
+    """Philox words of env `env`'s exploration noise at `tick` of rollout
+    episode `ep` (the first episode after rollout_alloc is ep = 1)."""
+    return philox4x32_10(int(seed) ^ 0x2F01E, (int(ep) << 20) | (tick + 2),
+                         env)
+
+
+def roll_reset_state(seed, ep, env):
+    """(th, thdot) the device reset gives env `env` at episode `ep`, in the
+    kernel's float32 arithmetic."""
+    v = philox4x32_10(int(seed) ^ 0xD011E, (int(ep) << 20) | 1, env)
+    f = np.float32
+    th = f(f(f(2.0) * u01(v[0]) - f(1.0)) * f(3.14159265358979))
+    td = f(f(2.0) * u01(v[1]) - f(1.0))
+    return th, td
 
 
 # ---------------------------------------------------------------------------

@@ -86,6 +86,75 @@ def test_descend_boundary_goes_left():
     assert orc.descend(st, 4, 15.0, 4) == 3
 
 
+def test_ring_oracle_matches_cpu_per_buffer():
+    """Across a wrapping sequence of batched adds the ring agrees with the
+    CPU prioritized buffer fed the same rows one by one."""
+    from d4pg_amd.replay.per import PrioritizedReplayBuffer
+    cap, tree_cap, O, A = 37, 64, 5, 2
+    alpha = 0.6
+    ring = orc.RingOracle(cap, tree_cap)
+    buf = PrioritizedReplayBuffer(cap, alpha)
+    rng = np.random.default_rng(0)
+    seen_wrap = False
+    for call, T in enumerate([20, 17, 1, 30, 80]):
+        s = rng.standard_normal((T, O)).astype("f")
+        a = rng.uniform(-1, 1, (T, A)).astype("f")
+        r = rng.uniform(-30, 0, T).astype("f")
+        s2 = rng.standard_normal((T, O)).astype("f")
+        d = (rng.random(T) < 0.3).astype("f")
+        # a different new-row priority per call, as after training
+        buf._max_priority = 1.0 + call
+        ring.add(s, a, r, s2, d, leaf=(1.0 + call) ** alpha)
+        for t in range(T):
+            buf.add(s[t], a[t], r[t], s2[t], d[t])
+        st = buf._store
+        assert (ring.size, ring.pos) == (st.size, st.pos)
+        seen_wrap |= ring.size == cap and ring.pos != 0
+        got = ring.occupied()
+        want = (st.states, st.actions, st.rewards, st.next_states, st.dones)
+        for g, w in zip(got, want):
+            assert np.array_equal(g, w[:st.size])
+        sum_t, min_t = ring.trees()
+        assert np.array_equal(sum_t, buf._it_sum.tree)
+        assert np.array_equal(min_t, buf._it_min.tree)
+    assert seen_wrap and ring.pos == (20 + 17 + 1 + 30 + 80) % cap
+    # T = 80 > 2 * capacity: every slot holds the last row mapped to it
+    assert np.array_equal(ring.rows["r"][(148 - 37 + np.arange(37)) % cap],
+                          r[-37:])
+
+
+def test_n01_moments_and_edges():
+    """Over 10^4 consecutive counters: mean within 0.05 of 0 (5 sigma of the
+    estimator, sigma = 0.01) and std within 0.05 of 1 (7 sigma, 0.007)."""
+    x = np.array([orc.n01(*orc.roll_noise_words(5, 1, 0, i)[:2])
+                  for i in range(10000)])
+    assert abs(x.mean()) < 0.05
+    assert abs(x.std() - 1.0) < 0.05
+    # u1 = 2^-32 (word 0) stays finite; u2 = 1 (word 2^32-1) is cos(2 pi)
+    top = np.sqrt(-2.0 * np.log(float(orc.u01(0))))
+    assert orc.n01(0, 0xFFFFFFFF) == pytest.approx(top, rel=1e-12)
+    assert 6.6 < top < 6.7
+
+
+def test_roll_streams_are_distinct_and_in_range():
+    seed = 9
+    th, td = zip(*[orc.roll_reset_state(seed, 1, i) for i in range(256)])
+    th, td = np.array(th), np.array(td)
+    assert th.dtype == np.float32 and td.dtype == np.float32
+    assert np.abs(th).max() <= np.pi and np.abs(td).max() <= 1.0
+    assert len(np.unique(th)) == 256 and len(np.unique(td)) == 256
+    # the counter packs (episode, tick + 2); tick 0 never collides with the
+    # reset counter (| 1), and episodes do not alias ticks
+    w = orc.roll_noise_words
+    assert w(seed, 1, 0, 3) != w(seed, 2, 0, 3)
+    assert w(seed, 1, 0, 3) != w(seed, 1, 1, 3)
+    assert w(seed, 1, 0, 3) != w(seed, 1, 0, 4)
+    assert w(seed, 1, 0, 3) == orc.philox4x32_10(seed ^ 0x2F01E,
+                                                 (1 << 20) | 2, 3)
+    th2, _ = orc.roll_reset_state(seed, 2, 0)
+    assert th2 != th[0]
+
+
 def test_is_weights_formula():
     leaves = np.array([0.5, 2.0, 1.0, 4.0, 0.25])
     st, mt = orc.build_trees(leaves, 8)
