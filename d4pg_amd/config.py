@@ -99,6 +99,9 @@ def make_parser() -> argparse.ArgumentParser:
                         "(env dynamics + policy + noise + n-step fold as "
                         "HIP kernels): 1 = force, 0 = off, -1 = auto "
                         "(on when the rank sees a GPU)")
+    p.add_argument("--her_ratio", default=0.8, type=float,
+                   help="probability that a step also stores a hindsight "
+                        "('future' strategy) copy when --her 1")
     return p
 
 
@@ -192,6 +195,7 @@ class D4PGConfig:
     noise_eps: float = 0.3
     vector_envs: int = 0
     gpu_actors: int = -1
+    her_ratio: float = 0.8
     extra: dict = field(default_factory=dict)
 
     @classmethod

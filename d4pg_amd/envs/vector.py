@@ -112,3 +112,96 @@ class VecNStep:
         if done_flag:
             self.reset()
         return out
+
+
+class VectorGoalReach:
+    """M independent GoalReachEnv instances in float32 numpy arrays: a point
+    in [-1, 1]^dim moved by a velocity action, sparse reward, success within
+    ``tol`` of the goal.  Unlike VectorPendulum, episodes end PER ENV (on
+    success): an env that has succeeded stays put (``alive`` 0) until the
+    next reset, so env i has its own length ``len[i] <= horizon``.
+
+    Host twin of the device goal rollout (ops/hip/engine_goal.hip): same
+    float32 state and the same update order — clip the action, move, clip
+    the position, record, then test success — so it serves both as the CPU
+    vector-actor path and as the parity oracle.  The whole episode is
+    recorded (``ep_pos [horizon+1, M, dim]``, ``ep_act [horizon, M, dim]``)
+    because the "future" HER relabel needs it (her.vector_add_experience).
+    """
+
+    def __init__(self, n_envs: int, dim: int = 2, speed: float = 0.1,
+                 tol: float = 0.05, seed: int | None = None,
+                 horizon: int = 50):
+        self.n = int(n_envs)
+        self.dim = int(dim)
+        self.obs_dim, self.act_dim = 2 * self.dim, self.dim
+        self.speed = np.float32(speed)
+        self.tol = np.float32(tol)
+        self.horizon = int(horizon)
+        self.rng = np.random.default_rng(seed)
+        self.set_state(np.zeros((self.n, self.dim), np.float32),
+                       np.zeros((self.n, self.dim), np.float32))
+
+    def compute_reward(self, achieved_goal, desired_goal, info=None):
+        """GoalReachEnv.compute_reward (float64 distance)."""
+        d = np.linalg.norm(np.asarray(achieved_goal, np.float64)
+                           - np.asarray(desired_goal, np.float64), axis=-1)
+        return np.where(d <= float(self.tol), 0.0, -1.0)
+
+    def set_state(self, pos, goal) -> np.ndarray:
+        """Start an episode from the given positions and goals.  No success
+        check here, as in GoalReachEnv.reset."""
+        self.pos = np.array(pos, np.float32).reshape(self.n, self.dim)
+        self.goal = np.array(goal, np.float32).reshape(self.n, self.dim)
+        self.alive = np.ones(self.n, bool)
+        self.len = np.zeros(self.n, np.int32)
+        self.succ = np.zeros(self.n, bool)
+        self.t = 0
+        self.ep_pos = np.zeros((self.horizon + 1, self.n, self.dim),
+                               np.float32)
+        self.ep_act = np.zeros((self.horizon, self.n, self.dim), np.float32)
+        self.ep_pos[0] = self.pos
+        return self._obs()
+
+    def reset(self) -> np.ndarray:
+        return self.set_state(
+            self.rng.uniform(-1.0, 1.0, (self.n, self.dim)),
+            self.rng.uniform(-1.0, 1.0, (self.n, self.dim)))
+
+    def _obs(self) -> np.ndarray:
+        return np.concatenate([self.pos, self.goal], axis=1)
+
+    def distance(self) -> np.ndarray:
+        """float32 ||pos - goal||, summed over dims in ascending order as
+        the kernel does."""
+        d2 = np.zeros(self.n, np.float32)
+        for k in range(self.dim):
+            d = self.pos[:, k] - self.goal[:, k]
+            d2 = d2 + d * d
+        return np.sqrt(d2)
+
+    def step(self, actions: np.ndarray):
+        """actions [M, dim].  Returns (obs, reward, success, alive): reward
+        is 0 / -1 for the envs that moved (0 for those already finished),
+        success the per-env flag so far, alive the mask AFTER this step."""
+        if self.t >= self.horizon:
+            raise RuntimeError("VectorGoalReach: step past the horizon")
+        live = self.alive.copy()
+        a = np.clip(np.asarray(actions, np.float32), -1.0, 1.0)
+        self.ep_act[self.t][live] = a[live]
+        new = np.clip(self.pos + self.speed * a, np.float32(-1.0),
+                      np.float32(1.0)).astype(np.float32)
+        self.pos[live] = new[live]
+        self.t += 1
+        self.ep_pos[self.t][live] = self.pos[live]
+        self.len[live] = self.t
+        hit = live & (self.distance() <= self.tol)
+        self.succ |= hit
+        self.alive &= ~hit
+        reward = np.where(live & ~hit, -1.0, 0.0).astype(np.float32)
+        return self._obs(), reward, self.succ.copy(), self.alive.copy()
+
+    def episode(self):
+        """(ep_pos, ep_act, len, succ, goal) of the episode so far."""
+        return (self.ep_pos, self.ep_act, self.len.copy(), self.succ.copy(),
+                self.goal.copy())

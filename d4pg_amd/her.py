@@ -97,3 +97,104 @@ def add_experience(replay_buffer, env, episode, her: bool = False,
             written += 1
         del her_folder
     return written
+
+
+# ---------------------------------------------------------------------------
+# vectorized goal episodes (VectorGoalReach / the device goal rollout)
+# ---------------------------------------------------------------------------
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = 0xFFFFFFFF
+
+# seed-xor constant of the device HER stream (engine_goal.hip goal_her_draw)
+HER_STREAM = 0x4E12E
+
+
+def philox4x32_10(seed: int, ctr_hi: int, ctr_lo: int):
+    """philox4x32-10 in the engine's calling convention: 64-bit seed -> key,
+    ctr_lo -> counter words 0,1 and ctr_hi -> counter words 2,3."""
+    seed, ctr_hi, ctr_lo = int(seed), int(ctr_hi), int(ctr_lo)
+    c0, c1 = ctr_lo & _U32, (ctr_lo >> 32) & _U32
+    c2, c3 = ctr_hi & _U32, (ctr_hi >> 32) & _U32
+    k0, k1 = seed & _U32, (seed >> 32) & _U32
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0, p1 & _U32,
+                          (p0 >> 32) ^ c3 ^ k1, p0 & _U32)
+        k0, k1 = (k0 + _PHILOX_W0) & _U32, (k1 + _PHILOX_W1) & _U32
+    return c0, c1, c2, c3
+
+
+class PhiloxHerRng:
+    """The ``rng`` add_experience needs, drawing what the device relabel
+    draws for env ``env`` of rollout episode ``episode``: the t-th call of
+    ``random()`` takes one philox draw keyed by (seed ^ HER_STREAM,
+    (episode << 20) | t, env); the following ``integers(t, T)`` returns
+    ``t + w1 % (T - t)`` from the same draw.
+
+    The kernel hits when ``u <= her_ratio`` with u in (0, 1] float32;
+    add_experience skips when ``random() >= her_ratio``.  ``random()``
+    returns the float32 just below u, so for a float32-representable ratio
+    the two tests agree on every draw (vector_add_experience rounds the
+    ratio to float32 before passing it on)."""
+
+    def __init__(self, seed: int, episode: int, env: int):
+        self.seed, self.episode, self.env = int(seed), int(episode), int(env)
+        self._t = -1
+        self._w = None
+
+    def random(self) -> float:
+        self._t += 1
+        self._w = philox4x32_10(self.seed ^ HER_STREAM,
+                                (self.episode << 20) | self._t, self.env)
+        u = np.float32(np.float32(np.float32(self._w[0]) + np.float32(1.0))
+                       * np.float32(2.3283064e-10))
+        return float(np.nextafter(u, np.float32(0.0)))
+
+    def integers(self, low: int, high: int) -> int:
+        return int(low) + self._w[1] % (int(high) - int(low))
+
+
+def vector_add_experience(replay_buffer, env, ep_pos, ep_act, length, succ,
+                          goal, her: bool = True, her_ratio: float = 0.8,
+                          n_steps: int = 1, gamma: float = 0.99,
+                          rng=None) -> int:
+    """Store the recorded episodes of M vectorized goal envs, in the order
+    the device emit writes them: env by env, each env's n-step folded real
+    rows by ascending t, then its HER rows by ascending t — i.e. the scalar
+    add_experience called once per env.
+
+    ep_pos [>=T+1, M, D], ep_act [>=T, M, D], length [M], succ [M] and
+    goal [M, D] are what VectorGoalReach.episode() / the device's
+    goal_rollout_episode() record.  ``env`` supplies compute_reward.  Only
+    an env's last step, and only when it succeeded, is terminal (the step
+    limit is not, as in rollout_episode).  ``rng`` is a numpy Generator
+    shared by all envs, or a callable ``env_index -> rng`` (PhiloxHerRng
+    for the device's own draws).  Returns the number of rows written."""
+    ep_pos = np.asarray(ep_pos, np.float32)
+    ep_act = np.asarray(ep_act, np.float32)
+    goal = np.asarray(goal, np.float32)
+    if rng is None:
+        rng = np.random.default_rng()
+    ratio = float(np.float32(her_ratio))
+    written = 0
+    for i in range(ep_pos.shape[1]):
+        T = int(length[i])
+        g = goal[i]
+
+        def dict_obs(p):
+            return {"observation": p, "achieved_goal": p, "desired_goal": g}
+
+        episode = []
+        for t in range(T):
+            nxt = ep_pos[t + 1, i]
+            done = bool(succ[i]) and t == T - 1
+            episode.append((dict_obs(ep_pos[t, i]), ep_act[t, i],
+                            float(np.asarray(env.compute_reward(nxt, g))),
+                            dict_obs(nxt), done, {"is_success": done}))
+        written += add_experience(
+            replay_buffer, env, episode, her=her, her_ratio=ratio,
+            n_steps=n_steps, gamma=gamma,
+            rng=rng(i) if callable(rng) else rng)
+    return written

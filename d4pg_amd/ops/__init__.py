@@ -333,6 +333,49 @@ class FusedEngine:
     def rollout_info(self):
         return self.ext.rollout_info(self.h)
 
+    # -- GPU-resident goal rollout (device GoalReach env + noise + n-step
+    # fold + "future" HER relabel, rows written straight into this engine's
+    # on-HBM replay; see ops/hip/engine_goal.hip) --
+    def goal_rollout_alloc(self, n_envs, n_steps, horizon=50, gamma=0.99,
+                           speed=0.1, tol=0.05, her_ratio=0.8,
+                           noise="gaussian", eps=0.3, ou_theta=0.15,
+                           ou_sigma=0.2, ou_mu=0.0, seed=0):
+        kind = {"gaussian": 0, "ou": 1}[noise]
+        self.ext.goal_rollout_alloc(
+            self.h, int(n_envs), int(n_steps), int(horizon), float(gamma),
+            float(speed), float(tol), float(her_ratio), kind, float(eps),
+            float(ou_theta), float(ou_sigma), float(ou_mu), int(seed))
+
+    def goal_rollout_run(self, episodes=1, reset=True, use_graph=True):
+        """Run whole episodes on-device (one hipGraph per episode when
+        reset=True); returns (env_steps, rows_emitted, successes) summed
+        over the episodes, all three read back from device words —
+        env_steps is the sum of the per-env episode lengths."""
+        return tuple(self.ext.goal_rollout_run(
+            self.h, int(episodes), bool(reset), bool(use_graph)))
+
+    def goal_rollout_set_state(self, pos, goal):
+        self.ext.goal_rollout_set_state(self.h, torch.as_tensor(pos),
+                                        torch.as_tensor(goal))
+
+    def goal_rollout_info(self):
+        return self.ext.goal_rollout_info(self.h)
+
+    def goal_rollout_episode(self):
+        """The last episode as the device recorded it: ep_pos
+        [horizon+1, M, D], ep_act [horizon, M, D], goal [M, D], len [M] and
+        succ [M] (steps past an env's len are stale)."""
+        return dict(self.ext.goal_rollout_episode(self.h))
+
+    def rollout_last_rows(self):
+        """Host copy of the rows of the LAST rollout episode only, in write
+        order, from its replay base and row count (replay_rows() returns
+        every occupied slot)."""
+        base, count = self.ext.rollout_last(self.h)
+        s, a, r, s2, d = self.ext.replay_slice(self.h, int(base), int(count))
+        return (s.numpy(), a.numpy(), r.numpy().ravel(), s2.numpy(),
+                d.numpy().ravel())
+
     def replay_rows(self):
         """Host copy of the occupied replay rows (s, a, r, s2, d) — used
         by GPU actor ranks to ship device-generated transitions to the

@@ -28,6 +28,7 @@
 #include "engine_layer.hip"
 #include "engine_rowblock.hip"
 #include "engine_rollout.hip"
+#include "engine_goal.hip"
 #include "engine_mfma.hip"
 #include "engine_persistent.hip"
 
@@ -814,12 +815,16 @@ public:
     hipGraph_t roll_graph = nullptr;
     hipGraphExec_t roll_graph_exec = nullptr;
     int roll_emits_per_ep = 0;
+    // which producer owns roll_pool_ and the episode graph
+    enum { ROLL_NONE = 0, ROLL_PENDULUM = 1, ROLL_GOAL = 2 };
+    int roll_kind_ = ROLL_NONE;
 
     void rollout_free() {
         if (roll_graph_exec) { hipGraphExecDestroy(roll_graph_exec);
                                roll_graph_exec = nullptr; }
         if (roll_graph) { hipGraphDestroy(roll_graph); roll_graph = nullptr; }
         if (roll_pool_) { hipFree(roll_pool_); roll_pool_ = nullptr; }
+        roll_kind_ = ROLL_NONE;
     }
 
     void rollout_alloc(int M, int nsteps, int horizon, float gamma,
@@ -867,10 +872,11 @@ public:
         a.cnt = ws.cnt;
         roll_ = a;
         roll_emits_per_ep = horizon - nsteps + 1;
+        roll_kind_ = ROLL_PENDULUM;
     }
 
-    void roll_fwd_chain() {
-        const int M = roll_.M;
+    // the policy forward obs [M][obs] -> act [M][act] between two ticks
+    void roll_fwd_chain(const float* obs, float* act, int M) {
         // (the tanh head takes the plain MFMA launch here, not the split-K
         // head pair: dw_parts is sized for the learner batch, not for M)
         auto run = [&](const float* x, const LayerDesc& l, float* y,
@@ -879,10 +885,10 @@ public:
             if (fwd_uses_mfma(M)) launch_fwd_mfma(j);
             else launch_fwd_valu(j);
         };
-        run(roll_.obs, anet.l[0], r_h1, ACT_RELU);
+        run(obs, anet.l[0], r_h1, ACT_RELU);
         run(r_h1, anet.l[1], r_h2, ACT_NONE);   // fc2->fc2_2 no-act quirk
         run(r_h2, anet.l[2], r_h3, ACT_RELU);
-        run(r_h3, anet.l[3], roll_.act, ACT_TANH);
+        run(r_h3, anet.l[3], act, ACT_TANH);
     }
 
     void rollout_enqueue_episode(bool reset) {
@@ -894,7 +900,7 @@ public:
                                stream, a);
         int emit_k = 0;
         for (int t = 0; t < a.horizon; ++t) {
-            roll_fwd_chain();
+            roll_fwd_chain(a.obs, a.act, a.M);
             int ek = (t >= a.n - 1) ? emit_k : -1;
             int done = (t == a.horizon - 1) ? 1 : 0;
             hipLaunchKernelGGL(k_roll_tick, dim3(wgs), dim3(256), 0, stream,
@@ -911,7 +917,7 @@ public:
     }
 
     void rollout_run(int episodes, bool reset, bool use_graph) {
-        if (!roll_pool_)
+        if (roll_kind_ != ROLL_PENDULUM)
             throw std::runtime_error("rollout_alloc first");
         if (use_graph && reset) {
             if (!roll_graph_exec) {
@@ -933,7 +939,7 @@ public:
 
     // test hook: inject exact env state (parity vs the numpy oracle)
     void rollout_set_state(const float* th, const float* td, int M) {
-        if (!roll_pool_ || M != roll_.M)
+        if (roll_kind_ != ROLL_PENDULUM || M != roll_.M)
             throw std::runtime_error("rollout_set_state: bad M");
         HIP_CHECK(hipMemcpy(roll_.th, th, M * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(roll_.thdot, td, M * 4, hipMemcpyHostToDevice));
@@ -948,6 +954,179 @@ public:
         // as k_roll_reset leaves it: the OU process starts at mu
         std::vector<float> ou(M, roll_.ou_mu);
         HIP_CHECK(hipMemcpy(roll_.ou_x, ou.data(), M * 4,
+                            hipMemcpyHostToDevice));
+    }
+
+    // ---------------- GPU-resident goal rollout + HER (engine_goal.hip) ----
+    // Shares the pool pointer, the hidden buffers, the episode graph and
+    // rollout_free() with the Pendulum rollout; one of the two is allocated
+    // at a time (roll_kind_).
+    GoalRollArgs goal_{};
+
+    // rows one episode can emit at most: every env runs to the step limit
+    // and every step gets a hindsight row
+    static long goal_episode_max(long M, long nsteps, long horizon) {
+        return M * (horizon - nsteps + 1) + M * horizon;
+    }
+
+    void goal_rollout_alloc(int M, int nsteps, int horizon, float gamma,
+                            float speed, float tol, float her_ratio,
+                            int noise_kind, float eps, float ou_theta,
+                            float ou_sigma, float ou_mu, uint64_t seed) {
+        if (cfg.act < 1 || cfg.obs != 2 * cfg.act)
+            throw std::runtime_error(
+                "device goal rollout needs obs = [pos, goal] (obs == 2*act)");
+        if (M < 1 || M > 65536)
+            throw std::runtime_error("goal rollout: n_envs not in [1, 65536]");
+        if (nsteps < 1 || horizon < nsteps)
+            throw std::runtime_error("goal rollout horizon < n_steps");
+        if (horizon >= (1 << 20))
+            throw std::runtime_error("goal rollout horizon >= 2^20");
+        if (cfg.capacity < goal_episode_max(M, nsteps, horizon))
+            throw std::runtime_error(
+                "goal rollout: replay capacity below one episode's maximum "
+                "M*(horizon-n+1) + M*horizon rows (two rows of one episode "
+                "would share a slot)");
+        rollout_free();
+        GoalRollArgs a{};
+        const int D = cfg.act, H = cfg.hidden;
+        a.M = M; a.D = D; a.n = nsteps; a.horizon = horizon;
+        a.gamma = gamma; a.eps = eps; a.ou_theta = ou_theta;
+        a.ou_sigma = ou_sigma; a.ou_mu = ou_mu; a.ou_dt = 1e-2f;
+        a.speed = speed; a.tol = tol; a.her_ratio = her_ratio;
+        a.noise_kind = noise_kind; a.seed = seed;
+        a.per_alpha = cfg.per_alpha;
+        long off = 0;
+        auto sub = [&](long nelem) {            // nelem 4-byte words
+            long o = off;
+            off += (nelem * 4 + 255) & ~255L;
+            return o;
+        };
+        const long MD = (long)M * D;
+        long o_pos = sub(MD), o_goal = sub(MD), o_obs = sub(2 * MD),
+             o_act = sub(MD), o_ou = sub(MD), o_alive = sub(M),
+             o_len = sub(M), o_succ = sub(M),
+             o_epp = sub((long)(horizon + 1) * MD),
+             o_epa = sub((long)horizon * MD), o_cnt = sub(M),
+             o_off = sub(2L * M), o_ep = sub(16),
+             o_h1 = sub((long)M * H), o_h2 = sub((long)M * H),
+             o_h3 = sub((long)M * H);
+        HIP_CHECK(hipMalloc(&roll_pool_, off));
+        HIP_CHECK(hipMemset(roll_pool_, 0, off));
+        // the episode kernels run on the engine's non-blocking stream
+        HIP_CHECK(hipDeviceSynchronize());
+        char* base = (char*)roll_pool_;
+        a.pos =(float*)(base + o_pos); a.goal = (float*)(base + o_goal);
+        a.obs = (float*)(base + o_obs); a.act = (float*)(base + o_act);
+        a.ou_x = (float*)(base + o_ou);
+        a.alive = (int*)(base + o_alive); a.len = (int*)(base + o_len);
+        a.succ = (int*)(base + o_succ);
+        a.ep_pos = (float*)(base + o_epp); a.ep_act = (float*)(base + o_epa);
+        a.count = (int*)(base + o_cnt);
+        a.offset = (long long*)(base + o_off);
+        a.ep_state = (long long*)(base + o_ep);
+        r_h1 = (float*)(base + o_h1); r_h2 = (float*)(base + o_h2);
+        r_h3 = (float*)(base + o_h3);
+        a.rs = ws.rs; a.ra = ws.ra; a.rr = ws.rr; a.rs2 = ws.rs2; a.rd = ws.rd;
+        a.sum_tree = ws.sum_tree; a.min_tree = ws.min_tree;
+        a.tree_cap = ws.tree_cap; a.capacity = cfg.capacity;
+        a.cnt = ws.cnt;
+        goal_ = a;
+        roll_kind_ = ROLL_GOAL;
+    }
+
+    void goal_enqueue_episode(bool reset) {
+        GoalRollArgs& a = goal_;
+        int wgs = ceil_div(a.M, 256);
+        hipLaunchKernelGGL(k_goal_begin, dim3(1), dim3(64), 0, stream, a);
+        if (reset)
+            hipLaunchKernelGGL(k_goal_reset, dim3(wgs), dim3(256), 0,
+                               stream, a);
+        for (int t = 0; t < a.horizon; ++t) {
+            roll_fwd_chain(a.obs, a.act, a.M);
+            hipLaunchKernelGGL(k_goal_tick, dim3(wgs), dim3(256), 0, stream,
+                               a, t);
+        }
+        hipLaunchKernelGGL(k_goal_count, dim3(wgs), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(k_goal_scan, dim3(1), dim3(GOAL_SCAN_THREADS), 0,
+                           stream, a);
+        // one wave per env, four to a workgroup
+        int ewgs = ceil_div(a.M, 4);
+        hipLaunchKernelGGL(k_goal_emit, dim3(ewgs > 2048 ? 2048 : ewgs),
+                           dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(k_goal_end, dim3(1), dim3(64), 0, stream, a);
+        for (long lo = ws.tree_cap / 2; lo >= 1; lo >>= 1)
+            hipLaunchKernelGGL(k_tree_build_level, dim3(1024), dim3(256), 0,
+                               stream, ws.sum_tree, ws.min_tree, lo, 2 * lo);
+    }
+
+    // Totals over the episodes of one goal_rollout_run call, read from the
+    // device words: rows emitted, successes, env steps (sum of lengths).
+    struct GoalTotals { long long rows, successes, env_steps; };
+
+    GoalTotals goal_rollout_run(int episodes, bool reset, bool use_graph) {
+        if (roll_kind_ != ROLL_GOAL)
+            throw std::runtime_error("goal_rollout_alloc first");
+        HIP_CHECK(hipMemsetAsync(goal_.ep_state + 5, 0, 3 * 8, stream));
+        if (use_graph && reset) {
+            if (!roll_graph_exec) {
+                HIP_CHECK(hipStreamBeginCapture(
+                    stream, hipStreamCaptureModeThreadLocal));
+                goal_enqueue_episode(true);
+                HIP_CHECK(hipStreamEndCapture(stream, &roll_graph));
+                HIP_CHECK(hipGraphInstantiate(&roll_graph_exec, roll_graph,
+                                              nullptr, nullptr, 0));
+            }
+            for (int e = 0; e < episodes; ++e)
+                HIP_CHECK(hipGraphLaunch(roll_graph_exec, stream));
+        } else {
+            for (int e = 0; e < episodes; ++e)
+                goal_enqueue_episode(reset);
+        }
+        long long w[3];
+        HIP_CHECK(hipMemcpyAsync(w, goal_.ep_state + 5, sizeof(w),
+                                 hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        return {w[0], w[1], w[2]};
+    }
+
+    // the per-episode device words of the last episode: [0] philox epoch,
+    // [1] replay base, [2] rows emitted, [3] successes, [4] env steps
+    void goal_rollout_words(long long (&w)[5]) {
+        if (roll_kind_ != ROLL_GOAL)
+            throw std::runtime_error("goal_rollout_alloc first");
+        HIP_CHECK(hipMemcpy(w, goal_.ep_state, sizeof(w),
+                            hipMemcpyDeviceToHost));
+    }
+
+    // test hook: inject exact env state, leaving everything else as
+    // k_goal_reset leaves it
+    void goal_rollout_set_state(const float* pos, const float* goal, int M) {
+        if (roll_kind_ != ROLL_GOAL || M != goal_.M)
+            throw std::runtime_error("goal_rollout_set_state: bad M");
+        const int D = goal_.D;
+        const long MD = (long)M * D;
+        std::vector<float> obs(2 * MD), ou(MD, goal_.ou_mu);
+        for (int i = 0; i < M; ++i)
+            for (int k = 0; k < D; ++k) {
+                obs[(long)i * 2 * D + k] = pos[(long)i * D + k];
+                obs[(long)i * 2 * D + D + k] = goal[(long)i * D + k];
+            }
+        std::vector<int> alive(M, 1);
+        HIP_CHECK(hipMemcpy(goal_.pos, pos, MD * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(goal_.goal, goal, MD * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(goal_.obs, obs.data(), 2 * MD * 4,
+                            hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(goal_.ep_pos, pos, MD * 4,
+                            hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(goal_.ou_x, ou.data(), MD * 4,
+                            hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(goal_.alive, alive.data(), M * 4,
+                            hipMemcpyHostToDevice));
+        std::vector<int> zero(M, 0);
+        HIP_CHECK(hipMemcpy(goal_.len, zero.data(), M * 4,
+                            hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(goal_.succ, zero.data(), M * 4,
                             hipMemcpyHostToDevice));
     }
 

@@ -1,0 +1,318 @@
+// Device goal-reaching rollout with hindsight relabelling: M vectorized
+// GoalReach envs (a point in [-1,1]^D moved by a velocity action, sparse
+// reward), exploration noise, the n-step fold and the "future"-strategy HER
+// relabel, writing rows straight into the on-HBM replay.  Used by
+// Engine::goal_rollout_*; the policy forward between ticks is the same
+// chain the Pendulum rollout uses.  Host twins and parity oracles:
+// VectorGoalReach (d4pg_amd/envs/vector.py) and vector_add_experience
+// (d4pg_amd/her.py), which calls the scalar add_experience once per env.
+//
+// Unlike the Pendulum rollout, episodes end per env (on success), so the
+// number of rows an episode produces is data-dependent, and the relabel needs
+// the whole episode.  Ticks therefore only record (ep_pos, ep_act); after the
+// last tick the episode is counted per env (k_goal_count), the counts are
+// scanned over envs (k_goal_scan) and every env writes its rows densely at
+// its own offset (k_goal_emit) — no atomics, so placement is deterministic
+// and a graph replay equals the uncaptured launches bitwise.  Everything
+// data-dependent (lengths, counts, offsets, totals) lives in device memory,
+// so the whole episode is still one hipGraph.
+
+namespace d4pg {
+
+struct GoalRollArgs {
+    int M, D, n, horizon;
+    float gamma, eps, ou_theta, ou_sigma, ou_mu, ou_dt;
+    float speed, tol, her_ratio;
+    int noise_kind;                    // 0 = gaussian, 1 = OU
+    uint64_t seed;
+    float per_alpha;
+    // env + noise state: pos/goal/act/ou_x [M][D], obs [M][2D] = pos ‖ goal
+    float *pos, *goal, *obs, *act, *ou_x;
+    int *alive, *len, *succ;           // [M]
+    // episode buffers: ep_pos [horizon+1][M][D], ep_act [horizon][M][D]
+    float *ep_pos, *ep_act;
+    // rows per env and their exclusive scan [M]
+    int* count;
+    long long* offset;
+    // per-episode device words: [0] philox epoch, [1] replay base pos,
+    // [2] rows emitted, [3] successes, [4] env steps (sum of lengths);
+    // [5..7] the same three summed over the episodes of one run call
+    long long* ep_state;
+    // replay
+    float *rs, *ra, *rr, *rs2, *rd;
+    double *sum_tree, *min_tree;
+    long tree_cap, capacity;
+    Counters* cnt;
+};
+
+// sparse reward of GoalReachEnv.compute_reward: 0 within tol, else -1
+__device__ inline float goal_reward(const float* p, const float* g, int D,
+                                    float tol) {
+    float d2 = 0.0f;
+    for (int k = 0; k < D; ++k) {
+        float d = p[k] - g[k];
+        d2 += d * d;
+    }
+    return sqrtf(d2) <= tol ? 0.0f : -1.0f;
+}
+
+// HER draw of step t of env i (T = the env's episode length, t < T): whether
+// the step gets a hindsight row and, if so, the future index in [t, T) whose
+// achieved position becomes the goal.  u01 is in (0,1], so a ratio of 1
+// always hits and a ratio of 0 never does.
+__device__ inline bool goal_her_draw(const GoalRollArgs& a, long long ep,
+                                     int t, int i, int T, int& fut) {
+    if (!(a.her_ratio > 0.0f)) return false;
+    Philox4 w = philox4(a.seed ^ 0x4E12Eull,
+                        ((uint64_t)ep << 20) | (uint64_t)t, (uint64_t)i);
+    fut = t + (int)(w.v[1] % (uint32_t)(T - t));
+    return u01(w.v[0]) <= a.her_ratio;
+}
+
+// episode prologue: bump the philox epoch, latch the replay write base
+__global__ void k_goal_begin(GoalRollArgs a) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        a.ep_state[0] += 1;
+        a.ep_state[1] = a.cnt->pos;
+    }
+}
+
+// reset all M envs: pos and goal uniform in [-1,1]^D, OU state to mu, and
+// the first observation.  No success check here, as on the host.
+__global__ void k_goal_reset(GoalRollArgs a) {
+    long long ep = a.ep_state[0];
+    const int D = a.D;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.M;
+         i += gridDim.x * blockDim.x) {
+        for (int k = 0; k < D; ++k) {
+            Philox4 r = philox4(a.seed ^ 0xD011Eull,
+                                ((uint64_t)ep << 20) | 1u,
+                                ((uint64_t)k << 32) | (uint64_t)i);
+            float p = 2.0f * u01(r.v[0]) - 1.0f;
+            float g = 2.0f * u01(r.v[1]) - 1.0f;
+            a.pos[i * D + k] = p;
+            a.goal[i * D + k] = g;
+            a.obs[i * 2 * D + k] = p;
+            a.obs[i * 2 * D + D + k] = g;
+            a.ep_pos[(long)i * D + k] = p;
+            a.ou_x[i * D + k] = a.ou_mu;
+        }
+        a.alive[i] = 1;
+        a.len[i] = 0;
+        a.succ[i] = 0;
+    }
+}
+
+// one synchronized tick: envs that already succeeded do nothing; the others
+// take noise -> clip -> move -> record, and stop on success
+__global__ void k_goal_tick(GoalRollArgs a, int tick) {
+    long long ep = a.ep_state[0];
+    const int D = a.D, M = a.M;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M;
+         i += gridDim.x * blockDim.x) {
+        if (!a.alive[i]) continue;
+        for (int k = 0; k < D; ++k) {
+            // --- exploration noise, as k_roll_tick; dim k draws its own
+            // stream through the high half of ctr_lo ---
+            float u = a.act[i * D + k];
+            if (a.noise_kind == 0 && a.eps != 0.0f) {
+                Philox4 r = philox4(a.seed ^ 0x2F01Eull,
+                                    ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
+                                    ((uint64_t)k << 32) | (uint64_t)i);
+                u += a.eps * n01(r.v[0], r.v[1]);
+            } else if (a.noise_kind == 1) {
+                Philox4 r = philox4(a.seed ^ 0x2F01Eull,
+                                    ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
+                                    ((uint64_t)k << 32) | (uint64_t)i);
+                float x = a.ou_x[i * D + k];
+                x += a.ou_theta * (a.ou_mu - x) * a.ou_dt
+                     + a.ou_sigma * sqrtf(a.ou_dt) * n01(r.v[0], r.v[1]);
+                a.ou_x[i * D + k] = x;
+                u += a.eps * x;
+            }
+            u = fminf(fmaxf(u, -1.0f), 1.0f);
+            a.ep_act[((long)tick * M + i) * D + k] = u;
+
+            // --- GoalReachEnv._step ---
+            float p = a.pos[i * D + k] + a.speed * u;
+            p = fminf(fmaxf(p, -1.0f), 1.0f);
+            a.pos[i * D + k] = p;
+            a.obs[i * 2 * D + k] = p;
+            a.ep_pos[((long)(tick + 1) * M + i) * D + k] = p;
+        }
+        a.len[i] = tick + 1;
+        // the same test the emit's rewards use, on the stored position
+        if (goal_reward(a.pos + i * D, a.goal + i * D, D, a.tol) == 0.0f) {
+            a.succ[i] = 1;
+            a.alive[i] = 0;
+        }
+    }
+}
+
+// rows env i will write: the folded real rows plus one per HER hit
+__global__ void k_goal_count(GoalRollArgs a) {
+    long long ep = a.ep_state[0];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.M;
+         i += gridDim.x * blockDim.x) {
+        int T = a.len[i];
+        int c = T - a.n + 1 > 0 ? T - a.n + 1 : 0;
+        for (int t = 0; t < T; ++t) {
+            int fut;
+            c += goal_her_draw(a, ep, t, i, T, fut) ? 1 : 0;
+        }
+        a.count[i] = c;
+    }
+}
+
+// exclusive scan of count[] over the M envs into offset[], one workgroup.
+// Thread t sums a contiguous run of envs, the 1024 run sums are scanned by
+// wave 0 (16 per lane, then a shuffle scan over the 64 lanes), and every
+// thread walks its run again.  The episode's totals (rows, successes, env
+// steps) go to the per-episode words; the integer adds are order-free.
+#define GOAL_SCAN_THREADS 1024
+__global__ __launch_bounds__(GOAL_SCAN_THREADS)
+void k_goal_scan(GoalRollArgs a) {
+    __shared__ long long run_sum[GOAL_SCAN_THREADS];
+    __shared__ int acc[2];
+    const int tid = threadIdx.x, M = a.M;
+    const int per = (M + GOAL_SCAN_THREADS - 1) / GOAL_SCAN_THREADS;
+    const int lo = tid * per < M ? tid * per : M;
+    const int hi = lo + per < M ? lo + per : M;
+    if (tid < 2) acc[tid] = 0;
+    __syncthreads();
+    long long s = 0;
+    int steps = 0, succ = 0;
+    for (int i = lo; i < hi; ++i) {
+        s += a.count[i];
+        steps += a.len[i];
+        succ += a.succ[i];
+    }
+    run_sum[tid] = s;
+    if (steps) atomicAdd(&acc[0], steps);
+    if (succ) atomicAdd(&acc[1], succ);
+    __syncthreads();
+    if (tid < 64) {
+        const int q0 = tid * (GOAL_SCAN_THREADS / 64);
+        long long v = 0;
+        for (int q = 0; q < GOAL_SCAN_THREADS / 64; ++q) {
+            long long x = run_sum[q0 + q];
+            run_sum[q0 + q] = v;
+            v += x;
+        }
+        const long long own = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            long long y = __shfl_up(v, d, 64);
+            if (tid >= d) v += y;
+        }
+        const long long before = v - own;
+        for (int q = 0; q < GOAL_SCAN_THREADS / 64; ++q)
+            run_sum[q0 + q] += before;
+        if (tid == 63) {
+            a.ep_state[2] = v;
+            a.ep_state[3] = acc[1];
+            a.ep_state[4] = acc[0];
+        }
+    }
+    __syncthreads();
+    long long run = run_sum[tid];
+    for (int i = lo; i < hi; ++i) {
+        a.offset[i] = run;
+        run += a.count[i];
+    }
+}
+
+// one wave per env, lanes over the env's steps: real (n-step folded) rows by
+// ascending t, then the HER rows by ascending t, at (base + offset[i] + j) %
+// capacity — the order add_experience writes them.  HER-row positions come
+// from a ballot of the hit lanes; horizons past 64 loop in chunks of 64.
+__global__ __launch_bounds__(256)
+void k_goal_emit(GoalRollArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int wpb = blockDim.x >> 6;
+    const long long ep = a.ep_state[0], base = a.ep_state[1];
+    const double pa = per_leaf_value(a.cnt->max_priority, a.per_alpha);
+    const int D = a.D, M = a.M, O = 2 * a.D;
+    for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < M;
+         i += gridDim.x * wpb) {
+        const int T = a.len[i];
+        const int succ = a.succ[i];
+        const long long row0 = base + a.offset[i];
+        const int n_real = T - a.n + 1 > 0 ? T - a.n + 1 : 0;
+        const float* g = a.goal + (long)i * D;
+
+        // --- real rows: (pos_{t-n+1}‖g, a_{t-n+1}, sum gamma^k r,
+        // pos_{t+1}‖g, done); done only where the env's last step succeeded
+        // (the step limit is not a terminal here, as in her.py) ---
+        for (int j = lane; j < n_real; j += 64) {
+            const int t = j + a.n - 1;
+            float R = 0.0f, gk = 1.0f;
+            for (int k = 0; k < a.n; ++k) {
+                R += gk * goal_reward(
+                    a.ep_pos + ((long)(j + k + 1) * M + i) * D, g, D, a.tol);
+                gk *= a.gamma;
+            }
+            const long dst = (long)((row0 + j) % a.capacity);
+            const float* p0 = a.ep_pos + ((long)j * M + i) * D;
+            const float* p1 = a.ep_pos + ((long)(t + 1) * M + i) * D;
+            const float* ac = a.ep_act + ((long)j * M + i) * D;
+            for (int k = 0; k < D; ++k) {
+                a.rs[dst * O + k] = p0[k];
+                a.rs[dst * O + D + k] = g[k];
+                a.ra[dst * D + k] = ac[k];
+                a.rs2[dst * O + k] = p1[k];
+                a.rs2[dst * O + D + k] = g[k];
+            }
+            a.rr[dst] = R;
+            a.rd[dst] = (t == T - 1 && succ) ? 1.0f : 0.0f;
+            a.sum_tree[a.tree_cap + dst] = pa;
+            a.min_tree[a.tree_cap + dst] = pa;
+        }
+
+        // --- HER rows (one-step): (pos_t‖g', a_t, r', pos_{t+1}‖g',
+        // r' == 0) with g' = pos_{fut+1} ---
+        int hits_before = 0;
+        for (int c = 0; c < T; c += 64) {
+            const int t = c + lane;
+            int fut = 0;
+            const bool hit = t < T && goal_her_draw(a, ep, t, i, T, fut);
+            const unsigned long long m = __ballot(hit);
+            if (hit) {
+                const int j = n_real + hits_before
+                              + __popcll(m & ((1ull << lane) - 1ull));
+                const long dst = (long)((row0 + j) % a.capacity);
+                const float* p0 = a.ep_pos + ((long)t * M + i) * D;
+                const float* p1 = a.ep_pos + ((long)(t + 1) * M + i) * D;
+                const float* ng = a.ep_pos + ((long)(fut + 1) * M + i) * D;
+                const float* ac = a.ep_act + ((long)t * M + i) * D;
+                const float r = goal_reward(p1, ng, D, a.tol);
+                for (int k = 0; k < D; ++k) {
+                    a.rs[dst * O + k] = p0[k];
+                    a.rs[dst * O + D + k] = ng[k];
+                    a.ra[dst * D + k] = ac[k];
+                    a.rs2[dst * O + k] = p1[k];
+                    a.rs2[dst * O + D + k] = ng[k];
+                }
+                a.rr[dst] = r;
+                a.rd[dst] = r == 0.0f ? 1.0f : 0.0f;
+                a.sum_tree[a.tree_cap + dst] = pa;
+                a.min_tree[a.tree_cap + dst] = pa;
+            }
+            hits_before += __popcll(m);
+        }
+    }
+}
+
+// episode epilogue: advance the replay counters by the device-side total
+__global__ void k_goal_end(GoalRollArgs a) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        long long base = a.ep_state[1], total = a.ep_state[2];
+        a.cnt->pos = (base + total) % a.capacity;
+        long long sz = a.cnt->size + total;
+        a.cnt->size = sz > a.capacity ? a.capacity : sz;
+        a.ep_state[5] += total;
+        a.ep_state[6] += a.ep_state[3];
+        a.ep_state[7] += a.ep_state[4];
+    }
+}
+
+}  // namespace d4pg

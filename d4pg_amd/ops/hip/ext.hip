@@ -293,6 +293,128 @@ static py::dict rollout_info(int64_t h) {
     return d;
 }
 
+// ---- GPU-resident goal rollout + HER relabel (engine_goal.hip) ----
+static void goal_rollout_alloc(int64_t h, int64_t M, int64_t n_steps,
+                               int64_t horizon, double gamma, double speed,
+                               double tol, double her_ratio,
+                               int64_t noise_kind, double eps,
+                               double ou_theta, double ou_sigma, double ou_mu,
+                               int64_t seed) {
+    get(h).goal_rollout_alloc((int)M, (int)n_steps, (int)horizon,
+                              (float)gamma, (float)speed, (float)tol,
+                              (float)her_ratio, (int)noise_kind, (float)eps,
+                              (float)ou_theta, (float)ou_sigma, (float)ou_mu,
+                              (uint64_t)seed);
+}
+
+// (env_steps, rows_emitted, successes) over the episodes of this call
+static py::tuple goal_rollout_run(int64_t h, int64_t episodes, bool reset,
+                                  bool use_graph) {
+    Engine::GoalTotals t = get(h).goal_rollout_run((int)episodes, reset,
+                                                   use_graph);
+    return py::make_tuple((int64_t)t.env_steps, (int64_t)t.rows,
+                          (int64_t)t.successes);
+}
+
+static void goal_rollout_set_state(int64_t h, torch::Tensor pos,
+                                   torch::Tensor goal) {
+    Engine& e = get(h);
+    auto t1 = f32_contig(pos), t2 = f32_contig(goal);
+    TORCH_CHECK(t1.numel() == t2.numel(), "pos/goal size mismatch");
+    TORCH_CHECK(t1.numel() % e.cfg.act == 0, "pos is not [M, act]");
+    e.goal_rollout_set_state(t1.data_ptr<float>(), t2.data_ptr<float>(),
+                             (int)(t1.numel() / e.cfg.act));
+}
+
+static py::dict goal_rollout_info(int64_t h) {
+    Engine& e = get(h);
+    long long w[5];
+    e.goal_rollout_words(w);
+    py::dict d;
+    d["M"] = e.goal_.M;
+    d["D"] = e.goal_.D;
+    d["n"] = e.goal_.n;
+    d["horizon"] = e.goal_.horizon;
+    d["episode_max_rows"] = Engine::goal_episode_max(e.goal_.M, e.goal_.n,
+                                                     e.goal_.horizon);
+    d["episode"] = (int64_t)w[0];
+    d["base"] = (int64_t)w[1];
+    d["rows"] = (int64_t)w[2];
+    d["successes"] = (int64_t)w[3];
+    d["env_steps"] = (int64_t)w[4];
+    return d;
+}
+
+// test hook: the last episode as recorded on the device
+static py::dict goal_rollout_episode(int64_t h) {
+    Engine& e = get(h);
+    long long w[5];
+    e.goal_rollout_words(w);            // throws unless a goal rollout is up
+    const GoalRollArgs& a = e.goal_;
+    const long M = a.M, D = a.D, HOR = a.horizon;
+    auto f32 = [&](const float* src, std::vector<int64_t> shape) {
+        auto t = torch::empty(shape, torch::kFloat32);
+        HIP_CHECK(hipMemcpy(t.data_ptr<float>(), src, t.numel() * 4,
+                            hipMemcpyDeviceToHost));
+        return t;
+    };
+    auto i32 = [&](const int* src) {
+        auto t = torch::empty({M}, torch::kInt32);
+        HIP_CHECK(hipMemcpy(t.data_ptr<int>(), src, M * 4,
+                            hipMemcpyDeviceToHost));
+        return t;
+    };
+    py::dict d;
+    d["ep_pos"] = f32(a.ep_pos, {HOR + 1, M, D});
+    d["ep_act"] = f32(a.ep_act, {HOR, M, D});
+    d["goal"] = f32(a.goal, {M, D});
+    d["len"] = i32(a.len);
+    d["succ"] = i32(a.succ);
+    return d;
+}
+
+// Host copy of `count` replay rows starting at ring slot `base` (wrapping),
+// in ring order.
+static py::tuple replay_slice(int64_t h, int64_t base, int64_t count) {
+    Engine& e = get(h);
+    const long C = e.cfg.capacity;
+    TORCH_CHECK(base >= 0 && base < C && count >= 0 && count <= C,
+                "replay_slice out of range");
+    const int O = e.cfg.obs, A = e.cfg.act;
+    const long first = std::min<long>(count, C - base);
+    auto grab = [&](const float* src, long w) {
+        auto t = torch::empty({count, w}, torch::kFloat32);
+        if (first)
+            HIP_CHECK(hipMemcpy(t.data_ptr<float>(), src + base * w,
+                                first * w * 4, hipMemcpyDeviceToHost));
+        if (count > first)
+            HIP_CHECK(hipMemcpy(t.data_ptr<float>() + first * w, src,
+                                (count - first) * w * 4,
+                                hipMemcpyDeviceToHost));
+        return t;
+    };
+    return py::make_tuple(grab(e.ws.rs, O), grab(e.ws.ra, A),
+                          grab(e.ws.rr, 1), grab(e.ws.rs2, O),
+                          grab(e.ws.rd, 1));
+}
+
+// (base, rows) of the last rollout episode, of either kind
+static py::tuple rollout_last(int64_t h) {
+    Engine& e = get(h);
+    if (e.roll_kind_ == Engine::ROLL_GOAL) {
+        long long w[5];
+        e.goal_rollout_words(w);
+        return py::make_tuple((int64_t)w[1], (int64_t)w[2]);
+    }
+    if (e.roll_kind_ != Engine::ROLL_PENDULUM)
+        throw std::runtime_error("no rollout allocated");
+    long long w[2];
+    HIP_CHECK(hipMemcpy(w, e.roll_.ep_state, sizeof(w),
+                        hipMemcpyDeviceToHost));
+    return py::make_tuple((int64_t)w[1],
+                          (int64_t)e.roll_emits_per_ep * e.roll_.M);
+}
+
 static torch::Tensor actor_forward(int64_t h, torch::Tensor x) {
     Engine& e = get(h);
     auto t = f32_contig(x);
@@ -388,6 +510,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("rollout_run", &d4pg::rollout_run);
     mod.def("rollout_set_state", &d4pg::rollout_set_state);
     mod.def("rollout_info", &d4pg::rollout_info);
+    mod.def("goal_rollout_alloc", &d4pg::goal_rollout_alloc);
+    mod.def("goal_rollout_run", &d4pg::goal_rollout_run);
+    mod.def("goal_rollout_set_state", &d4pg::goal_rollout_set_state);
+    mod.def("goal_rollout_info", &d4pg::goal_rollout_info);
+    mod.def("goal_rollout_episode", &d4pg::goal_rollout_episode);
+    mod.def("replay_slice", &d4pg::replay_slice);
+    mod.def("rollout_last", &d4pg::rollout_last);
     mod.def("actor_forward", &d4pg::actor_forward);
     mod.def("read_buffer", &d4pg::read_buffer);
 }

@@ -45,7 +45,7 @@ import torch.distributed as dist
 from ..algo.d4pg import DDPG
 from ..config import critic_dist_info, noise_kwargs, run_dir_name
 from ..envs import make, obs_act_dims
-from ..her import add_experience, rollout_episode
+from ..her import add_experience, rollout_episode, vector_add_experience
 from ..ops import pack_net, unpack_net
 from ..utils.logging import Meter, SummaryWriter
 
@@ -232,6 +232,49 @@ class DistributedD4PG:
                 and args.env.startswith("Pendulum"):
             # every rank must agree on the wire size
             self.push_cap = int(args.vector_envs) * args.max_steps
+        # vectorized goal-reaching actor with HER: M GoalReach envs per
+        # actor rank (VectorGoalReach + vector_add_experience on the CPU);
+        # when the rank has a GPU, the device goal rollout instead — env,
+        # policy forward, noise, n-step fold and the "future" relabel as
+        # HIP kernels (ops/hip/engine_goal.hip), one hipGraph per episode.
+        self.goal_vec = None
+        self.goal_engine = False
+        self.her_ratio = float(getattr(args, "her_ratio", 0.8))
+        if (int(getattr(args, "vector_envs", 0)) > 0 and args.her
+                and args.env.startswith("GoalReach")):
+            m = int(args.vector_envs)
+            horizon = int(self.env._max_episode_steps)
+            # real + hindsight rows of one episode; every rank must agree
+            self.push_cap = 2 * m * horizon
+            if not self.is_learner and not self.is_evaluator:
+                from ..envs.vector import VectorGoalReach
+                self.goal_vec = VectorGoalReach(
+                    m, dim=self.env.dim, speed=self.env.speed,
+                    tol=self.env.tol, seed=seed + 17, horizon=horizon)
+                if (getattr(args, "noise", "gaussian") == "ou"):
+                    from ..noise import OrnsteinUhlenbeckProcess
+                    self.vec_noise = OrnsteinUhlenbeckProcess(
+                        (m, self.act_dim), mu=args.ou_mu,
+                        theta=args.ou_theta, sigma=args.ou_sigma,
+                        rng=np.random.default_rng(seed + 29))
+                if ga != 0 and torch.cuda.is_available():
+                    from ..ops import FusedEngine
+                    self.roll_engine = FusedEngine(
+                        obs_dim=self.obs_dim, act_dim=self.act_dim,
+                        hidden=256, n_atoms=args.n_atoms, batch=64,
+                        capacity=self.push_cap, v_min=args.v_min,
+                        v_max=args.v_max,
+                        gamma_n=args.gamma ** args.n_steps, tau=args.tau,
+                        lr_actor=1e-4, lr_critic=1e-4, seed=seed + 31)
+                    self.roll_engine.goal_rollout_alloc(
+                        m, args.n_steps, horizon=horizon, gamma=args.gamma,
+                        speed=self.env.speed, tol=self.env.tol,
+                        her_ratio=self.her_ratio,
+                        noise=getattr(args, "noise", "gaussian"),
+                        eps=self.noise_eps, ou_theta=args.ou_theta,
+                        ou_sigma=args.ou_sigma, ou_mu=args.ou_mu,
+                        seed=seed + 37)
+                    self.goal_engine = True
         self.blob_len = pack_net(self.agent.actor).numel() + 1
 
         self.grad_meter = Meter()
@@ -266,6 +309,13 @@ class DistributedD4PG:
             unpack_net(self.agent.actor, blob[:-1])
             self.global_step = int(blob[-1].item())
 
+    def _log_success(self, frac):
+        """Per-episode success fraction of the vectorized goal actor."""
+        self.success_frac = float(frac)
+        if self.args.debug:
+            print(f"[actor {self.rank}] step {self.global_step} episode "
+                  f"success {self.success_frac:.3f}", flush=True)
+
     def _collect(self):
         lb = _ListBuffer()
         if self.is_learner:
@@ -276,6 +326,44 @@ class DistributedD4PG:
                 0.95 * self.ewma + 0.05 * R
             print(f"[eval] step {self.global_step} return {R:.2f} "
                   f"ewma {self.ewma:.2f}", flush=True)
+            return lb
+        if self.goal_engine:
+            # device goal rollout: episodes end per env, so the row count
+            # and the env steps come back from the device words, and only
+            # the last episode's rows are shipped
+            from ..ops import pack_net as _pack
+            self.roll_engine.load_slab("actor", _pack(self.agent.actor))
+            env_steps, _, successes = self.roll_engine.goal_rollout_run(1)
+            lb.add_batch(*self.roll_engine.rollout_last_rows())
+            self.env_meter.add(env_steps)
+            self._log_success(successes / self.goal_vec.n)
+            return lb
+        if self.goal_vec is not None:
+            import torch as _t
+            vec = self.goal_vec
+            obs = vec.reset()
+            actor = self.agent.actor
+            if self.vec_noise is not None:
+                self.vec_noise.reset()
+            alive = vec.alive
+            with _t.no_grad():
+                for t in range(vec.horizon):
+                    if not alive.any():
+                        break
+                    a = actor(_t.from_numpy(obs)).numpy()
+                    if self.vec_noise is not None:
+                        a = a + self.noise_eps * self.vec_noise.sample()
+                    else:
+                        a = a + (self.noise_eps
+                                 * self.rng.standard_normal(a.shape))
+                    obs, _, _, alive = vec.step(a.astype(np.float32))
+            ep_pos, ep_act, length, succ, goal = vec.episode()
+            vector_add_experience(
+                lb, vec, ep_pos, ep_act, length, succ, goal, her=True,
+                her_ratio=self.her_ratio, n_steps=self.args.n_steps,
+                gamma=self.args.gamma, rng=self.rng)
+            self.env_meter.add(int(length.sum()))
+            self._log_success(float(succ.mean()))
             return lb
         if self.roll_engine is not None:
             # device rollout: load the freshly broadcast policy into the
@@ -315,7 +403,7 @@ class DistributedD4PG:
             ep, _, _ = rollout_episode(self.agent, self.env, noise=True)
             self.env_meter.add(len(ep))
             add_experience(lb, self.env, ep, her=bool(self.args.her),
-                           n_steps=self.args.n_steps, gamma=self.args.gamma,
+                           her_ratio=self.her_ratio, n_steps=self.args.n_steps, gamma=self.args.gamma,
                            rng=self.rng)
         return lb
 
