@@ -351,6 +351,9 @@ class DDPG:
                                                "state_dict"):
             st["beta_schedule"] = self.beta_schedule.state_dict()
             st["replay"] = self.replayBuffer.state_dict()
+        elif self._fused is not None:
+            # uniform replay on the engine: the on-HBM rows, no trees
+            st["replay"] = self.replayBuffer.state_dict()
         if self._fused is not None:
             # device-side optimizer state (Adam moments live in engine
             # slabs, not in the torch optimizers) + schedule counters
@@ -362,6 +365,8 @@ class DDPG:
                 "v_critic": eng.store_slab("v_critic"),
                 "counters": eng.counters(),
                 "seed": eng.info()["seed"],
+                # replay mode: a checkpoint loads only into the same mode
+                "prioritized": bool(eng.info()["prioritized"]),
             }
         # nn.Module.state_dict() returns REFERENCES to the live tensors —
         # continued training would silently mutate the checkpoint.  A
@@ -388,6 +393,16 @@ class DDPG:
                     % ("on-HBM" if gpu_format else "CPU",
                        "on-HBM" if have_gpu_buf else "CPU",
                        "hip" if gpu_format else "eager"))
+            ckpt_per = st.get("engine", {}).get("prioritized", True)
+            if gpu_format and ckpt_per != bool(self.prioritized_replay):
+                raise ValueError(
+                    "checkpoint replay mode (%s) does not match this "
+                    "agent's (%s) — there is no conversion between the two; "
+                    "build the agent with prioritized_replay=%r or pass "
+                    "load_replay=False"
+                    % ("prioritized" if ckpt_per else "uniform",
+                       "prioritized" if self.prioritized_replay
+                       else "uniform", ckpt_per))
         self.actor.load_state_dict(st["actor"])
         self.critic.load_state_dict(st["critic"])
         self.actor_target.load_state_dict(st["actor_target"])
@@ -401,6 +416,9 @@ class DDPG:
             if (load_replay and "replay" in st
                     and hasattr(self.replayBuffer, "load_state_dict")):
                 self.replayBuffer.load_state_dict(st["replay"])
+        elif (not self.prioritized_replay and load_replay and "replay" in st
+              and self._fused is not None):
+            self.replayBuffer.load_state_dict(st["replay"])
         if self._fused is not None and "engine" in st:
             eng = self._fused.engine
             eng.load_from_modules(self.actor, self.actor_target,

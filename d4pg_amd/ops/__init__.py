@@ -147,12 +147,21 @@ class GPUReplayAdapter:
                 + sum(len(b[2]) for b in self._batches))
 
     # -- exact resume (SURVEY §5 checkpoint row): snapshot/restore the
-    # on-HBM SoA store + sum/min trees --
+    # on-HBM SoA store + sum/min trees (zero-length on uniform replay) --
     def state_dict(self):
         self.flush()
         return dict(self.engine.ext.replay_state(self.engine.h))
 
     def load_state_dict(self, st):
+        snap_per = st["sum_tree"].numel() > 0
+        if snap_per != self.engine.prioritized:
+            raise ValueError(
+                "checkpoint replay mode (%s) does not match this engine's "
+                "(%s) — there is no conversion between the two; build the "
+                "agent with prioritized_replay=%r or pass load_replay=False"
+                % ("prioritized" if snap_per else "uniform",
+                   "prioritized" if self.engine.prioritized else "uniform",
+                   snap_per))
         self._pending.clear()
         self.engine.ext.load_replay_state(
             self.engine.h, st["s"], st["a"], st["r"], st["s2"], st["d"],
@@ -170,15 +179,23 @@ class FusedEngine:
     def __init__(self, obs_dim, act_dim, hidden, n_atoms, batch, capacity,
                  v_min, v_max, gamma_n, tau, lr_actor, lr_critic,
                  per_alpha=0.6, per_beta0=0.4, per_beta_iters=100000,
-                 per_eps=1e-6, seed=0, is_weighting=False):
+                 per_eps=1e-6, seed=0, is_weighting=False,
+                 prioritized=True, true_td_priorities=False):
+        """prioritized=False: uniform replay (an integer philox draw per
+        probe, IS weights exactly 1, no sum/min trees allocated or
+        maintained).  true_td_priorities: the written-back priority is
+        |E_m[z] - E_q[z]| + per_eps in place of the reference's <m, q>
+        proxy."""
         self.ext = load_extension()
         self.h = self.ext.create(
             obs_dim, act_dim, hidden, n_atoms, batch, capacity,
             float(v_min), float(v_max), float(gamma_n), float(tau),
             float(lr_actor), float(lr_critic), float(per_alpha),
             float(per_beta0), int(per_beta_iters), float(per_eps),
-            int(seed), bool(is_weighting))
+            int(seed), bool(is_weighting), bool(prioritized),
+            bool(true_td_priorities))
         self.batch = batch
+        self.prioritized = bool(prioritized)
         self._captured = 0
         self._persistent = bool(self.ext.info(self.h).get("persistent", False))
 
@@ -406,6 +423,8 @@ class FusedDDPGBridge:
             lr_actor=ddpg.optimizer_actor.param_groups[0]["lr"],
             lr_critic=ddpg.optimizer_critic.param_groups[0]["lr"],
             is_weighting=ddpg.is_weighting,
+            prioritized=ddpg.prioritized_replay,
+            true_td_priorities=ddpg.true_td_priorities,
             seed=0 if ddpg.rng is None else int(ddpg.rng.integers(1 << 31)))
         self.engine.load_from_modules(ddpg.actor, ddpg.actor_target,
                                       ddpg.critic, ddpg.critic_target)

@@ -100,7 +100,9 @@ public:
         ws.per_alpha = c.per_alpha; ws.per_beta0 = c.per_beta0;
         ws.per_beta_iters = (float)c.per_beta_iters;
         ws.is_weighting = c.is_weighting;
-        ws.seed = c.seed; ws.tree_cap = next_pow2(c.capacity);
+        ws.prioritized = c.prioritized; ws.true_td = c.true_td;
+        ws.seed = c.seed;
+        ws.tree_cap = has_trees() ? next_pow2(c.capacity) : 0;
         ws.n_actor = anet.n_params; ws.n_critic = cnet.n_params;
         for (int i = 0; i < 4; ++i) {
             ws.al[i] = anet.l[i];
@@ -124,6 +126,21 @@ public:
     int device_ = 0;
 
     bool persistent_fits_ = false;
+
+    // The one predicate every tree-touching launch is gated on.  Uniform
+    // replay allocates no sum/min trees (tree_cap 0, null pointers): the
+    // step samples by integer draw and skips the priority write-back, and
+    // the write side copies rows only.
+    bool has_trees() const { return cfg.prioritized != 0; }
+
+    // internal tree nodes from the leaves: one bandwidth-bound sweep per
+    // level (bulk ingest, synth_fill, once per rollout episode)
+    void launch_tree_rebuild(int wgs) {
+        if (!has_trees()) return;
+        for (long lo = ws.tree_cap / 2; lo >= 1; lo >>= 1)
+            hipLaunchKernelGGL(k_tree_build_level, dim3(wgs), dim3(256), 0,
+                               stream, ws.sum_tree, ws.min_tree, lo, 2 * lo);
+    }
 
     // the persistent grid barrier's timeout flag (gbar[176]); raised on
     // device when a p_bar spins out, fatal host-side — the engine state
@@ -179,8 +196,12 @@ public:
         ws.rs = carve<float>(C * O, off); ws.ra = carve<float>(C * A, off);
         ws.rr = carve<float>(C, off); ws.rs2 = carve<float>(C * O, off);
         ws.rd = carve<float>(C, off);
-        ws.sum_tree = carve<double>(2 * ws.tree_cap, off);
-        ws.min_tree = carve<double>(2 * ws.tree_cap, off);
+        if (has_trees()) {
+            ws.sum_tree = carve<double>(2 * ws.tree_cap, off);
+            ws.min_tree = carve<double>(2 * ws.tree_cap, off);
+        } else {
+            ws.sum_tree = ws.min_tree = nullptr;
+        }
         ws.cnt = carve<Counters>(1, off);
         ws.bs = carve<float>((long)B * O, off);
         ws.bs_b = carve<float>((long)B * O, off);
@@ -283,8 +304,9 @@ public:
                             hipMemcpyHostToDevice));
         // min-tree neutral element is +inf (memset zero would make every
         // unoccupied leaf the minimum and zero out all IS weights)
-        hipLaunchKernelGGL(k_fill_f64, dim3(1024), dim3(256), 0, nullptr,
-                           ws.min_tree, 2 * ws.tree_cap, HUGE_VAL);
+        if (has_trees())
+            hipLaunchKernelGGL(k_fill_f64, dim3(1024), dim3(256), 0, nullptr,
+                               ws.min_tree, 2 * ws.tree_cap, HUGE_VAL);
         HIP_CHECK(hipDeviceSynchronize());
     }
 
@@ -515,9 +537,14 @@ public:
         }
         if (mask & PH_ACTOR_APPLY) {
             launch_adam_lerp(true);
-            hipLaunchKernelGGL(k_per_update, dim3(1), dim3(256), 0, stream,
-                               ws.sum_tree, ws.min_tree, ws.tree_cap,
-                               ws.bidx, ws.pri, B, cfg.per_alpha, ws.cnt);
+            if (has_trees())
+                hipLaunchKernelGGL(k_per_update, dim3(1), dim3(256), 0,
+                                   stream, ws.sum_tree, ws.min_tree,
+                                   ws.tree_cap, ws.bidx, ws.pri, B,
+                                   cfg.per_alpha, ws.cnt);
+            else            // the counters still tick once per step
+                hipLaunchKernelGGL(k_tick_end, dim3(1), dim3(64), 0, stream,
+                                   ws.cnt);
         }
     }
 
@@ -565,7 +592,7 @@ public:
                            ws.p_t, ws.br, ws.bd, ws.q, ws.bw, ws.m_proj,
                            ws.dlog, ws.pri, ws.cnt,
                            B, K, cfg.v_min, cfg.v_max, cfg.gamma_n,
-                           cfg.per_eps, cfg.is_weighting);
+                           cfg.per_eps, cfg.is_weighting, cfg.true_td);
         // P11-14: critic backward L4..L1
         launch_bwd(ws.dlog, ws.c_h3, nullptr, ws.p_critic, ws.g_critic,
                    cnet.l[3], ws.d3, nullptr, ws.c_h3, ACT_RELU, true);
@@ -629,6 +656,7 @@ public:
         launch_adam_lerp(true);
         // P34: PER priority write-back by the per-level grid-wide repair
         // (the one-wg level-synced k_per_update serializes at this size)
+        if (has_trees()) {
         hipLaunchKernelGGL(k_per_leaves, dim3(ceil_div(B, 256)),
                            dim3(256), 0, stream, ws.sum_tree, ws.min_tree,
                            ws.tree_cap, ws.bidx, ws.pri, B, cfg.per_alpha,
@@ -642,6 +670,7 @@ public:
                                dim3(ceil_div((long)B * nlv, 256)),
                                dim3(256), 0, stream, ws.sum_tree, ws.min_tree,
                                ws.tree_cap, ws.bidx, B, h0, nlv);
+        }
         }
         hipLaunchKernelGGL(k_tick_end, dim3(1), dim3(64), 0, stream, ws.cnt);
     }
@@ -713,15 +742,13 @@ public:
                            ws.rs, ws.ra, ws.rr, ws.rs2, ws.rd, ws.sum_tree,
                            ws.min_tree, ws.tree_cap, cfg.capacity, n, cfg.obs,
                            cfg.act, seed, cfg.per_alpha);
-        for (long lo = ws.tree_cap / 2; lo >= 1; lo /= 2)
-            hipLaunchKernelGGL(k_tree_build_level, dim3(256), dim3(256), 0,
-                               stream, ws.sum_tree, ws.min_tree, lo,
-                               lo == 0 ? 1 : 2 * lo);
+        launch_tree_rebuild(256);
         Counters h{};
         HIP_CHECK(hipMemcpyAsync(&h, ws.cnt, sizeof(h), hipMemcpyDeviceToHost,
                                  stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        h.size = n; h.pos = n % cfg.capacity; h.max_priority = 1.0f;
+        h.size = n; h.pos = n % cfg.capacity;
+        if (has_trees()) h.max_priority = 1.0f;
         HIP_CHECK(hipMemcpy(ws.cnt, &h, sizeof(h), hipMemcpyHostToDevice));
     }
 
@@ -770,10 +797,7 @@ public:
                                cfg.capacity, (h.pos + skip) % cfg.capacity,
                                ing_s, ing_a, ing_r, ing_s2, ing_d, T, O, A,
                                pa);
-            for (long lo = ws.tree_cap / 2; lo >= 1; lo >>= 1)
-                hipLaunchKernelGGL(k_tree_build_level, dim3(1024),
-                                   dim3(256), 0, stream, ws.sum_tree,
-                                   ws.min_tree, lo, 2 * lo);
+            launch_tree_rebuild(1024);
             h.pos = (h.pos + skip + T) % cfg.capacity;
             h.size = h.size + T > cfg.capacity ? cfg.capacity : h.size + T;
             HIP_CHECK(hipMemcpyAsync(ws.cnt, &h, sizeof(h),
@@ -911,9 +935,7 @@ public:
                            (long)emit_k * a.M);
         // internal tree nodes: one bandwidth-bound full sweep per episode
         // (vs horizon x per-path repair) — leaves were set at emit
-        for (long lo = ws.tree_cap / 2; lo >= 1; lo >>= 1)
-            hipLaunchKernelGGL(k_tree_build_level, dim3(1024), dim3(256), 0,
-                               stream, ws.sum_tree, ws.min_tree, lo, 2 * lo);
+        launch_tree_rebuild(1024);
     }
 
     void rollout_run(int episodes, bool reset, bool use_graph) {
@@ -1055,9 +1077,7 @@ public:
         hipLaunchKernelGGL(k_goal_emit, dim3(ewgs > 2048 ? 2048 : ewgs),
                            dim3(256), 0, stream, a);
         hipLaunchKernelGGL(k_goal_end, dim3(1), dim3(64), 0, stream, a);
-        for (long lo = ws.tree_cap / 2; lo >= 1; lo >>= 1)
-            hipLaunchKernelGGL(k_tree_build_level, dim3(1024), dim3(256), 0,
-                               stream, ws.sum_tree, ws.min_tree, lo, 2 * lo);
+        launch_tree_rebuild(1024);
     }
 
     // Totals over the episodes of one goal_rollout_run call, read from the

@@ -80,6 +80,8 @@ struct EngineCfg {
     long per_beta_iters;
     uint64_t seed;
     int is_weighting;          // apply IS weights to the CE loss
+    int prioritized = 1;       // 0: uniform replay, no sum/min trees
+    int true_td = 0;           // priority |E_m[z] - E_q[z]| for <m, q>
 };
 
 // device-side counters (one small block)
@@ -124,8 +126,9 @@ struct StepArgs {
     float v_min, v_max, gamma_n, per_eps, tau, lr_actor, lr_critic;
     float per_alpha, per_beta0, per_beta_iters;
     int is_weighting;
+    int prioritized, true_td;
     uint64_t seed;
-    long tree_cap;
+    long tree_cap;                   // 0 (and null trees) on uniform replay
     long n_actor, n_critic;
     LayerDesc al[4], cl[4];
     // params / grads / moments / targets

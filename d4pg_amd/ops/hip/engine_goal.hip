@@ -230,7 +230,8 @@ void k_goal_emit(GoalRollArgs a) {
     const int lane = threadIdx.x & 63;
     const int wpb = blockDim.x >> 6;
     const long long ep = a.ep_state[0], base = a.ep_state[1];
-    const double pa = per_leaf_value(a.cnt->max_priority, a.per_alpha);
+    const double pa = a.sum_tree
+        ? per_leaf_value(a.cnt->max_priority, a.per_alpha) : 0.0;
     const int D = a.D, M = a.M, O = 2 * a.D;
     for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < M;
          i += gridDim.x * wpb) {
@@ -264,8 +265,10 @@ void k_goal_emit(GoalRollArgs a) {
             }
             a.rr[dst] = R;
             a.rd[dst] = (t == T - 1 && succ) ? 1.0f : 0.0f;
-            a.sum_tree[a.tree_cap + dst] = pa;
-            a.min_tree[a.tree_cap + dst] = pa;
+            if (a.sum_tree) {                   // null: uniform replay
+                a.sum_tree[a.tree_cap + dst] = pa;
+                a.min_tree[a.tree_cap + dst] = pa;
+            }
         }
 
         // --- HER rows (one-step): (pos_t‖g', a_t, r', pos_{t+1}‖g',
@@ -294,8 +297,10 @@ void k_goal_emit(GoalRollArgs a) {
                 }
                 a.rr[dst] = r;
                 a.rd[dst] = r == 0.0f ? 1.0f : 0.0f;
-                a.sum_tree[a.tree_cap + dst] = pa;
-                a.min_tree[a.tree_cap + dst] = pa;
+                if (a.sum_tree) {
+                    a.sum_tree[a.tree_cap + dst] = pa;
+                    a.min_tree[a.tree_cap + dst] = pa;
+                }
             }
             hits_before += __popcll(m);
         }

@@ -85,7 +85,7 @@ __global__ void k_project_ce(const float* __restrict__ p_t,
                              float* __restrict__ pri, Counters* cnt,
                              int B, int K, float v_min, float v_max,
                              float gamma_n, float per_eps,
-                             int is_weighting) {
+                             int is_weighting, int true_td) {
     int lane = threadIdx.x & 63;
     int wrow = threadIdx.x / 64;
     int wpb = blockDim.x / 64;
@@ -107,8 +107,11 @@ __global__ void k_project_ce(const float* __restrict__ p_t,
         float scale = (is_weighting && w) ? w[row] : 1.f;
         CeRow g = ce_grad_row(mv, qv, scale, B);
         if (lane < K) dlogits[(long)row * K + lane] = g.dz;
+        float pr = ce_priority_row(mv, qv, g.dot,
+                                   c51_atom(v_min, v_max, K, lane), true_td,
+                                   per_eps);
         if (lane == 0) {
-            pri[row] = g.dot + per_eps;
+            pri[row] = pr;
             ce_acc += scale * g.ce / (float)B;
         }
         __builtin_amdgcn_wave_barrier();

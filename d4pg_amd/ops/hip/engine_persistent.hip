@@ -546,7 +546,8 @@ __device__ inline void p_adam_lerp(float* __restrict__ p,
     }
 }
 
-// PER sample + gather phase (one wave per probe, like k_per_sample)
+// sample + gather phase, PER or uniform (one wave per probe, like
+// k_per_sample)
 __device__ inline void p_sample(const StepArgs& g, int wg0,
                                 long long epoch, long long beta_t,
                                 float* bs_out) {
@@ -559,7 +560,7 @@ __device__ inline void p_sample(const StepArgs& g, int wg0,
     int probe = ((int)blockIdx.x - wg0) * 4 + (threadIdx.x >> 6);
     int lane = threadIdx.x & 63;
     if (probe >= g.B) return;
-    per_sample_probe<true>(g, bs_out, probe, lane, epoch, beta_t);
+    sample_probe<true>(g, bs_out, probe, lane, epoch, beta_t);
 }
 
 // merged projection + CE-grad phase: the wave that projects row b's target
@@ -585,8 +586,11 @@ __device__ inline void p_project_ce(const StepArgs& g, float* lds,
     float scale = (g.is_weighting && g.bw) ? g.bw[row] : 1.f;
     CeRow r = ce_grad_row(mv, qv, scale, g.B);
     if (lane < K) g.dlog[(long)row * K + lane] = r.dz;
+    float pri = ce_priority_row(mv, qv, r.dot,
+                                c51_atom(g.v_min, g.v_max, K, lane),
+                                g.true_td, g.per_eps);
     if (lane == 0) {
-        g.pri[row] = r.dot + g.per_eps;
+        g.pri[row] = pri;
         atomicAdd(&g.cnt->loss_critic, scale * r.ce / (float)g.B);
     }
 }
@@ -635,7 +639,9 @@ __device__ inline void p_policy_grad(const StepArgs& g,
 // PER write-back (k_per_update without its counter tick — k_step_persistent
 // advances the counters once per launch); one workgroup, `owner_wg`, does it
 __device__ inline void p_per_update(const StepArgs& g, int owner_wg) {
-    if ((int)blockIdx.x != owner_wg) return;
+    // uniform replay has no trees: skip the work, never a barrier arrival
+    // (the callers' t_bar / p_bar stay where they are)
+    if ((int)blockIdx.x != owner_wg || !g.prioritized) return;
     per_write_leaves(g.sum_tree, g.min_tree, g.tree_cap, g.bidx, g.pri, g.B,
                      g.per_alpha, g.cnt);
     per_repair_paths(g.sum_tree, g.min_tree, g.tree_cap, g.B, 256,

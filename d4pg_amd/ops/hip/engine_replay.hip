@@ -7,8 +7,8 @@
 
 namespace d4pg {
 
-// ---- PER sample + gather ---------------------------------------------------
-// One wave per probe (per_sample_probe); first kernel of a row-block or wide
+// ---- sample + gather (PER or uniform) --------------------------------------
+// One wave per probe (sample_probe); first kernel of a row-block or wide
 // step, reading the schedule position from the device counters.
 __global__ void k_per_sample(StepArgs g) {
     int probe = blockIdx.x * (blockDim.x / 64) + (threadIdx.x / 64);
@@ -20,8 +20,8 @@ __global__ void k_per_sample(StepArgs g) {
         g.cnt->loss_critic = 0.f;
         g.cnt->loss_actor = 0.f;
     }
-    per_sample_probe<false>(g, g.bs, probe, lane, g.cnt->rng_epoch,
-                            g.cnt->beta_t);
+    sample_probe<false>(g, g.bs, probe, lane, g.cnt->rng_epoch,
+                        g.cnt->beta_t);
 }
 
 // ---- PER priority write-back (K12 update path) ------------------------------
@@ -104,6 +104,8 @@ __global__ void k_tick_end(Counters* cnt) { tick_counters(cnt); }
 // ---- replay ingestion (batched add) -----------------------------------------
 // T transitions appended at the ring position with priority max_priority^alpha,
 // then one level-synced repair pass.  Single workgroup (T can exceed threads).
+// Uniform replay passes null trees: the write-side kernels below (and the
+// rollouts' emit kernels) then copy rows only.
 __global__ void k_replay_add(float* __restrict__ rs, float* __restrict__ ra,
                              float* __restrict__ rr, float* __restrict__ rs2,
                              float* __restrict__ rd,
@@ -120,7 +122,8 @@ __global__ void k_replay_add(float* __restrict__ rs, float* __restrict__ ra,
     int tid = threadIdx.x;
     // skip: rows the host dropped from a call longer than the ring
     long pos0 = (cnt->pos + skip) % capacity;
-    double pa = per_leaf_value(cnt->max_priority, alpha);
+    const bool trees = sum_tree != nullptr;
+    double pa = trees ? per_leaf_value(cnt->max_priority, alpha) : 0.0;
     // copy rows (grid-stride inside the WG over T*max(obs,act) elems)
     for (long e = tid; e < (long)T * obs; e += blockDim.x) {
         long t = e / obs, k = e % obs;
@@ -137,12 +140,15 @@ __global__ void k_replay_add(float* __restrict__ rs, float* __restrict__ ra,
         long slot = (pos0 + t) % capacity;
         rr[slot] = tr[t];
         rd[slot] = td[t];
-        sum_tree[tree_cap + slot] = pa;
-        min_tree[tree_cap + slot] = pa;
+        if (trees) {
+            sum_tree[tree_cap + slot] = pa;
+            min_tree[tree_cap + slot] = pa;
+        }
     }
     __syncthreads();
-    per_repair_paths(sum_tree, min_tree, tree_cap, T, blockDim.x,
-                     [&](int t) { return tree_cap + (pos0 + t) % capacity; });
+    if (trees)
+        per_repair_paths(sum_tree, min_tree, tree_cap, T, blockDim.x, [&](int t) {
+            return tree_cap + (pos0 + t) % capacity; });
     if (tid == 0) {
         cnt->pos = (pos0 + T) % capacity;
         cnt->size = cnt->size + T > capacity ? capacity : cnt->size + T;
@@ -185,8 +191,10 @@ __global__ void k_replay_copy(float* __restrict__ rs, float* __restrict__ ra,
         long slot = (pos0 + t) % capacity;
         rr[slot] = tr[t];
         rd[slot] = td[t];
-        sum_tree[tree_cap + slot] = pa;
-        min_tree[tree_cap + slot] = pa;
+        if (sum_tree) {
+            sum_tree[tree_cap + slot] = pa;
+            min_tree[tree_cap + slot] = pa;
+        }
     }
 }
 
@@ -210,8 +218,10 @@ __global__ void k_synth_fill(float* rs, float* ra, float* rr, float* rs2,
         }
         rr[i] = -u01(r.v[1]) * 10.f;
         rd[i] = (u01(r.v[2]) < 0.01f) ? 1.f : 0.f;
-        sum_tree[tree_cap + i] = 1.0;     // max_priority(1)^alpha
-        min_tree[tree_cap + i] = 1.0;
+        if (sum_tree) {
+            sum_tree[tree_cap + i] = 1.0;     // max_priority(1)^alpha
+            min_tree[tree_cap + i] = 1.0;
+        }
     }
 }
 

@@ -90,7 +90,8 @@ __global__ void k_roll_tick(RollArgs a, int tick, int slot, int emit_k,
                             int done) {
     long long ep = a.ep_state[0];
     long long base = a.ep_state[1];
-    double pa = per_leaf_value(a.cnt->max_priority, a.per_alpha);
+    double pa = a.sum_tree
+        ? per_leaf_value(a.cnt->max_priority, a.per_alpha) : 0.0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.M;
          i += gridDim.x * blockDim.x) {
         // --- exploration noise (K11): per-env per-tick philox stream ---
@@ -155,8 +156,10 @@ __global__ void k_roll_tick(RollArgs a, int tick, int slot, int emit_k,
             a.rs2[dst * 3 + 1] = o1;
             a.rs2[dst * 3 + 2] = o2;
             a.rd[dst] = (float)done;
-            a.sum_tree[a.tree_cap + dst] = pa;
-            a.min_tree[a.tree_cap + dst] = pa;
+            if (a.sum_tree) {                   // null: uniform replay
+                a.sum_tree[a.tree_cap + dst] = pa;
+                a.min_tree[a.tree_cap + dst] = pa;
+            }
         }
     }
 }

@@ -165,8 +165,11 @@ k_critic_rowblock(StepArgs g) {
             L.r2[lane] = r.dz;
             g.dlog[(long)b * K + lane] = r.dz;
         }
+        float pri = ce_priority_row(mv, qv, r.dot,
+                                    c51_atom(g.v_min, g.v_max, K, lane),
+                                    g.true_td, g.per_eps);
         if (lane == 0) {
-            g.pri[b] = r.dot + g.per_eps;
+            g.pri[b] = pri;
             atomicAdd(&g.cnt->loss_critic, scale * r.ce / (float)g.B);
         }
     }

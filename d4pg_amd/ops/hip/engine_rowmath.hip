@@ -1,6 +1,7 @@
 // Row and probe formulas of the train step, one device implementation each:
 // the wave-wide softmax, the C51 projection scatter, the CE and policy-head
-// gradients, the PER descent / IS weight / sample+gather, the leaf write and
+// gradients and the row priority, the PER descent / IS weight, the uniform
+// draw, the sample+gather both share, the leaf write and
 // level-synchronised path repair of the sum/min trees, the schedule-counter
 // tick and Adam's bias-correction terms.  Used by all three paths
 // (persistent, row-block, wide) and by the replay kernels, which is what keeps
@@ -83,6 +84,22 @@ __device__ __forceinline__ CeRow ce_grad_row(float mv, float qv, float scale,
     return {scale * (qv - mv) / (float)B, dot, ce};
 }
 
+// The row's replay priority from ce_grad_row's inputs and its dot, on every
+// lane: the reference's proxy <m, q> + eps, or with true_td the TD error of
+// the expectations |E_m[z] - E_q[z]| + eps (z = lane's atom).  The two extra
+// wave reductions run only under true_td (wave-uniform).
+__device__ __forceinline__ float ce_priority_row(float mv, float qv,
+                                                 float dot, float z,
+                                                 int true_td, float per_eps) {
+    if (!true_td) return dot + per_eps;
+    float em = mv * z, eq = qv * z;
+    for (int s = 32; s > 0; s >>= 1) {
+        em += __shfl_xor(em, s, 64);
+        eq += __shfl_xor(eq, s, 64);
+    }
+    return fabsf(em - eq) + per_eps;
+}
+
 // Policy-head gradient of one row through the softmax:
 // L = -(1/B) sum_b sum_k q_k z_k  =>  dlogits_j = -q_j (z_j - E_q[z]) / B.
 // e returns E_q[z], wave-reduced (the row's loss is -e / B).
@@ -145,23 +162,38 @@ __device__ __forceinline__ float per_is_weight(double p, double p_min,
     return (float)(pow(p * (double)n, (double)-beta) / max_w);
 }
 
+// Gather tail of both sample helpers: lane 0 holds the drawn slot and has
+// written bidx / bw / br / bd; all lanes cooperatively gather the transition
+// row into the batch SoA, states into bs_out.  NT keeps the gathered replay
+// rows (random, never re-read) out of L2.
+template <bool NT>
+__device__ __forceinline__ void sample_gather_row(const StepArgs& g,
+                                                  float* bs_out, int probe,
+                                                  int lane, long idx) {
+    auto ld = [](const float* p) {
+        return NT ? __builtin_nontemporal_load(p) : *p;
+    };
+    idx = __shfl(idx, 0, 64);
+    for (int k = lane; k < g.O; k += 64) {
+        bs_out[(long)probe * g.O + k] = ld(&g.rs[idx * g.O + k]);
+        g.bs2[(long)probe * g.O + k] = ld(&g.rs2[idx * g.O + k]);
+    }
+    for (int k = lane; k < g.A; k += 64)
+        g.ba[(long)probe * g.A + k] = ld(&g.ra[idx * g.A + k]);
+}
+
 // PER sample + gather of one probe by one wave: lane 0 walks the sum tree
-// (double, exact) and writes the IS weight, all lanes then cooperatively
-// gather the transition row into the batch SoA, states into bs_out.  epoch /
-// beta_t are the schedule values of the step being sampled.  NT also keeps
-// the gathered replay rows (random, never re-read) out of L2.
+// (double, exact) and writes the IS weight, then the gather tail.  epoch /
+// beta_t are the schedule values of the step being sampled.
 template <bool NT>
 __device__ __forceinline__ void per_sample_probe(const StepArgs& g,
                                                  float* bs_out, int probe,
                                                  int lane, long long epoch,
                                                  long long beta_t) {
-    auto ld = [](const float* p) {
-        return NT ? __builtin_nontemporal_load(p) : *p;
-    };
     long long n = g.cnt->size;
     double total = g.sum_tree[1];
     float beta = per_beta(beta_t, g.per_beta0, g.per_beta_iters);
-    long idx;
+    long idx = 0;
     if (lane == 0) {
         Philox4 r = philox4(g.seed, (uint64_t)epoch, (uint64_t)probe);
         double mass = (double)u01(r.v[0]) * total;
@@ -173,13 +205,44 @@ __device__ __forceinline__ void per_sample_probe(const StepArgs& g,
         g.br[probe] = g.rr[idx];
         g.bd[probe] = g.rd[idx];
     }
-    idx = __shfl(idx, 0, 64);
-    for (int k = lane; k < g.O; k += 64) {
-        bs_out[(long)probe * g.O + k] = ld(&g.rs[idx * g.O + k]);
-        g.bs2[(long)probe * g.O + k] = ld(&g.rs2[idx * g.O + k]);
+    sample_gather_row<NT>(g, bs_out, probe, lane, idx);
+}
+
+// Uniform sample + gather of one probe (g.prioritized == 0; no tree is
+// touched): the same philox key and counters as the PER draw, so rng_epoch
+// means the same in both modes.  The slot is the high half of the 64 x 64-bit
+// integer product x * n, x the draw's first two words: every slot of any
+// replay size is reachable, where a float32 u01 * n stops at 2^24 distinct
+// values.  beta_t is unused; the IS weight is exactly 1.
+template <bool NT>
+__device__ __forceinline__ void uniform_sample_probe(const StepArgs& g,
+                                                     float* bs_out, int probe,
+                                                     int lane, long long epoch,
+                                                     long long /*beta_t*/) {
+    long idx = 0;
+    if (lane == 0) {
+        unsigned long long n = (unsigned long long)g.cnt->size;
+        Philox4 r = philox4(g.seed, (uint64_t)epoch, (uint64_t)probe);
+        unsigned long long x = ((unsigned long long)r.v[0] << 32) | r.v[1];
+        idx = (long)__umul64hi(x, n);       // floor(x * n / 2^64) < n
+        g.bidx[probe] = idx;
+        g.bw[probe] = 1.0f;
+        g.br[probe] = g.rr[idx];
+        g.bd[probe] = g.rd[idx];
     }
-    for (int k = lane; k < g.A; k += 64)
-        g.ba[(long)probe * g.A + k] = ld(&g.ra[idx * g.A + k]);
+    sample_gather_row<NT>(g, bs_out, probe, lane, idx);
+}
+
+// the engine's replay mode picks the draw (wave-uniform: a kernel argument)
+template <bool NT>
+__device__ __forceinline__ void sample_probe(const StepArgs& g, float* bs_out,
+                                             int probe, int lane,
+                                             long long epoch,
+                                             long long beta_t) {
+    if (g.prioritized)
+        per_sample_probe<NT>(g, bs_out, probe, lane, epoch, beta_t);
+    else
+        uniform_sample_probe<NT>(g, bs_out, probe, lane, epoch, beta_t);
 }
 
 // ---- PER write-back --------------------------------------------------------

@@ -25,7 +25,8 @@ static int64_t create(int64_t obs, int64_t act, int64_t hidden, int64_t atoms,
                       double v_max, double gamma_n, double tau,
                       double lr_actor, double lr_critic, double per_alpha,
                       double per_beta0, int64_t per_beta_iters,
-                      double per_eps, int64_t seed, bool is_weighting) {
+                      double per_eps, int64_t seed, bool is_weighting,
+                      bool prioritized, bool true_td) {
     EngineCfg c{};
     c.obs = (int)obs; c.act = (int)act; c.hidden = (int)hidden;
     c.atoms = (int)atoms; c.batch = (int)batch;
@@ -36,6 +37,7 @@ static int64_t create(int64_t obs, int64_t act, int64_t hidden, int64_t atoms,
     c.per_alpha = (float)per_alpha; c.per_beta0 = (float)per_beta0;
     c.per_beta_iters = per_beta_iters; c.per_eps = (float)per_eps;
     c.seed = (uint64_t)seed; c.is_weighting = is_weighting ? 1 : 0;
+    c.prioritized = prioritized ? 1 : 0; c.true_td = true_td ? 1 : 0;
     int64_t h = g_next++;
     g_engines[h] = std::make_unique<Engine>(c);
     return h;
@@ -48,7 +50,9 @@ static py::dict info(int64_t h) {
     py::dict d;
     d["n_params_actor"] = e.anet.n_params;
     d["n_params_critic"] = e.cnet.n_params;
-    d["tree_cap"] = e.ws.tree_cap;
+    d["tree_cap"] = e.ws.tree_cap;      // 0 on uniform replay (no trees)
+    d["prioritized"] = e.cfg.prioritized != 0;
+    d["true_td"] = e.cfg.true_td != 0;
     d["persistent"] = e.step_path() == Engine::PATH_PERSISTENT;
     d["seed"] = (int64_t)e.cfg.seed;
     py::list al, cl;
@@ -148,7 +152,8 @@ static void set_schedule(int64_t h, int64_t steps_done, double max_priority) {
     HIP_CHECK(hipMemcpy(e.ws.cnt, &c, sizeof(c), hipMemcpyHostToDevice));
 }
 
-// on-HBM replay snapshot: SoA rows [0, size) + both segment trees
+// on-HBM replay snapshot: SoA rows [0, size) + both segment trees (zero-
+// length on uniform replay)
 static py::dict replay_state(int64_t h) {
     Engine& e = get(h);
     Counters c{};
@@ -170,10 +175,12 @@ static py::dict replay_state(int64_t h) {
     d["d"] = grab(e.ws.rd, n, 1);
     auto st = torch::empty({2 * e.ws.tree_cap}, torch::kFloat64);
     auto mt = torch::empty({2 * e.ws.tree_cap}, torch::kFloat64);
-    HIP_CHECK(hipMemcpy(st.data_ptr<double>(), e.ws.sum_tree,
-                        2 * e.ws.tree_cap * 8, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(mt.data_ptr<double>(), e.ws.min_tree,
-                        2 * e.ws.tree_cap * 8, hipMemcpyDeviceToHost));
+    if (e.has_trees()) {
+        HIP_CHECK(hipMemcpy(st.data_ptr<double>(), e.ws.sum_tree,
+                            2 * e.ws.tree_cap * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(mt.data_ptr<double>(), e.ws.min_tree,
+                            2 * e.ws.tree_cap * 8, hipMemcpyDeviceToHost));
+    }
     d["sum_tree"] = st;
     d["min_tree"] = mt;
     d["size"] = c.size;
@@ -190,7 +197,12 @@ static void load_replay_state(int64_t h, torch::Tensor s, torch::Tensor a,
     Engine& e = get(h);
     const int O = e.cfg.obs, A = e.cfg.act;
     long n = size;
-    TORCH_CHECK(sum_tree.numel() == 2 * e.ws.tree_cap, "tree size mismatch");
+    TORCH_CHECK(sum_tree.numel() == 2 * e.ws.tree_cap &&
+                    min_tree.numel() == 2 * e.ws.tree_cap,
+                "tree size mismatch: the snapshot holds ", sum_tree.numel(),
+                " sum-tree nodes, this engine ", 2 * e.ws.tree_cap,
+                e.has_trees() ? " (prioritized replay)"
+                              : " (uniform replay keeps no trees)");
     auto put = [&](float* dst, torch::Tensor t, long rows, long w) {
         auto tt = f32_contig(t);
         TORCH_CHECK(tt.numel() == rows * w, "replay slab size mismatch");
@@ -205,10 +217,12 @@ static void load_replay_state(int64_t h, torch::Tensor s, torch::Tensor a,
     put(e.ws.rd, dn, n, 1);
     auto st = sum_tree.to(torch::kFloat64).contiguous().cpu();
     auto mt = min_tree.to(torch::kFloat64).contiguous().cpu();
-    HIP_CHECK(hipMemcpy(e.ws.sum_tree, st.data_ptr<double>(),
-                        2 * e.ws.tree_cap * 8, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(e.ws.min_tree, mt.data_ptr<double>(),
-                        2 * e.ws.tree_cap * 8, hipMemcpyHostToDevice));
+    if (e.has_trees()) {
+        HIP_CHECK(hipMemcpy(e.ws.sum_tree, st.data_ptr<double>(),
+                            2 * e.ws.tree_cap * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(e.ws.min_tree, mt.data_ptr<double>(),
+                            2 * e.ws.tree_cap * 8, hipMemcpyHostToDevice));
+    }
     Counters c{};
     HIP_CHECK(hipMemcpy(&c, e.ws.cnt, sizeof(c), hipMemcpyDeviceToHost));
     c.size = size;
@@ -468,7 +482,11 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
     long n = 1;
     for (long s : ent.shape) n *= s;
     torch::Tensor out;
-    if (ent.is_long) {
+    if (n == 0) {                       // the trees of a uniform engine
+        out = torch::empty(ent.shape, ent.is_long ? torch::kInt64
+                           : ent.is_double ? torch::kFloat64
+                                           : torch::kFloat32);
+    } else if (ent.is_long) {
         out = torch::empty(ent.shape, torch::kInt64);
         HIP_CHECK(hipMemcpy(out.data_ptr<int64_t>(), ent.p, n * 8,
                             hipMemcpyDeviceToHost));
