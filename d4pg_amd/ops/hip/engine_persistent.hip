@@ -3,8 +3,9 @@
 // the step (and an nsteps loop of steps) as ~27 layer-parallel phases over 96
 // co-resident workgroups separated by a software grid barrier (tree arrival +
 // write-once go-flag).  Each GEMM/dX phase tiles 4 rows x 64 cols per
-// workgroup with register-batched, double-buffered LDS staging; PER write-back
-// and the next step's tree sampling hide under the dW/Adam phases.  At B=64
+// workgroup with register-batched, double-buffered LDS staging; at B <= 64 the
+// PER write-back, the next step's sampling and its critic forward hide beside
+// the row-local quad chains (elsewhere under the dW/Adam phases).  At B=64
 // the step is latency-bound (PMC: 3% VALUBusy), so the design maximizes
 // memory-level parallelism, not FLOPs.
 
@@ -46,11 +47,32 @@ namespace d4pg {
 #define PLDS_FLOATS (2 * 4 * PXMAX + 2 * 64 * 68 + 64)
 
 // phase timing probe: wg0/lane0 stamps the wall clock (100 MHz constant
-// clock) after each barrier of the FIRST step of a launch; read back via
-// read_buffer("tstamp") to locate slow phases.
-#define PTIME(g, s, i) \
-    do { if (blockIdx.x == 0 && threadIdx.x == 0 && (s) == 0) \
+// clock) after each barrier of ONE step of a launch; read back via
+// read_buffer("tstamp") to locate slow phases.  The stamped step is `pts`
+// (k_step_persistent: step 1 of a multi-step launch, the first that runs
+// the pipelined steady-state schedule; step 0 of a one-step launch).
+// PTIMEW stamps from workgroup w instead (the crews' end stamps, slots
+// 52-55).
+#define PTIMEW(g, s, i, w) \
+    do { if ((int)blockIdx.x == (w) && threadIdx.x == 0 && (s) == pts) \
         (g).tstamp[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define PTIME(g, s, i) PTIMEW(g, s, i, 0)
+
+// The barriers' two fences are one-directional: the release before an
+// arrival writes this workgroup's stores back, the acquire after the wait
+// drops the CU's stale L1 lines.  (__threadfence() does both; two of them
+// per barrier cost the flagship step ~19 us over the 7 grid and 17 quad
+// barriers of its critical path — 4616 -> 5041 steps/s, NOTES.md.)  The
+// explicit vmcnt wait keeps the arrival, and the loads after the barrier,
+// behind the fence's own wait.
+__device__ inline void bar_release() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+__device__ inline void bar_acquire() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
 
 // software grid barrier — tree arrival + write-once go-flag.  Safe because
 // all PNWG workgroups are co-resident (256 wgs of 256 threads, one per CU
@@ -72,7 +94,7 @@ __device__ inline void p_bar(unsigned long long* gb,
     __syncthreads();
     round += 1;
     if (threadIdx.x == 0) {
-        __threadfence();                       // release: flush our writes
+        bar_release();                         // flush our writes
         int grp = blockIdx.x & 7;
         unsigned long long old = atomicAdd(&gb[grp << 4], 1ull);
         if (old + 1 == round * (PNWG >> 3)) {  // last of the group
@@ -105,7 +127,7 @@ __device__ inline void p_bar(unsigned long long* gb,
                 if ((spins & 63) == 0 && *err) break;
             }
         }
-        __threadfence();                       // acquire: invalidate L1
+        bar_acquire();                         // invalidate L1
     }
     __syncthreads();
 }
@@ -123,7 +145,7 @@ __device__ inline void q_bar(unsigned long long* qc,
     __syncthreads();
     qround += 4;
     if (threadIdx.x == 0) {
-        __threadfence();
+        bar_release();
         atomicAdd(qc, 1ull);
         volatile unsigned long long* f = qc;
         long spins = 0;
@@ -131,7 +153,7 @@ __device__ inline void q_bar(unsigned long long* qc,
             if (++spins > (1L << 26)) break;
             __builtin_amdgcn_s_sleep(1);
         }
-        __threadfence();
+        bar_acquire();
     }
     __syncthreads();
 }
@@ -146,7 +168,7 @@ __device__ inline void t_bar(unsigned long long* tc,
     __syncthreads();
     trnd += members;
     if (threadIdx.x == 0) {
-        __threadfence();
+        bar_release();
         atomicAdd(tc, 1ull);
         volatile unsigned long long* f = tc;
         long spins = 0;
@@ -154,7 +176,7 @@ __device__ inline void t_bar(unsigned long long* tc,
             if (++spins > (1L << 26)) break;
             __builtin_amdgcn_s_sleep(1);
         }
-        __threadfence();
+        bar_acquire();
     }
     __syncthreads();
 }
@@ -678,87 +700,137 @@ k_step_persistent(StepArgs g, int nsteps) {
     const int QW = ((B + 3) / 4) * 4;        // wgs used by the quad chains
     const bool otail = (QW + 32 <= PNWG) && (B <= 128);
     unsigned long long trnd = ctr[1280];
+    const int pts = nsteps > 1 ? 1 : 0;      // the step PTIME stamps
 
     for (int s = 0; s < nsteps; ++s) {
         float* bs_cur = ((bt0 + s) & 1) ? g.bs_b : g.bs;
         float* bs_nxt = ((bt0 + s) & 1) ? g.bs : g.bs_b;
                PTIME(g, s, 0);
-        // PH0: PER sample + batch gather (only on a launch's first step —
-        // later steps were pre-sampled under the previous actor-Adam,
-        // whose 64 overlap wgs cover 256 probes)
-        if (s == 0 || B > (PNWG - PNWG * 3 / 4) * 4) {
-            p_sample(g, 0, ep0 + s, bt0 + s, bs_cur);
-            p_bar(ctr, tgt);
-        }
-        PTIME(g, s, 1);
-        // PH1: four independent L1s (16 wgs each)
-        if (wg < PW4)
-            p_fwd(lds, g.bs2, nullptr, at.w1, at.b1, g.at_h1, B, O, 0, H,
-                  ACT_RELU, wg, PW4);
-        else if (wg < 2 * PW4) {
-            if (!otail || s == 0)     // else precomputed by the tail crew
+        // Steady-state (pipelined) step: at B <= 64 every step of a launch
+        // but the first finds its batch sampled and its whole critic
+        // forward (c_h1..c_h3, q) and ct_h1 already computed — the tail
+        // crew did that under the previous step's policy block, after the
+        // critic Adam made this step's critic weights final.  Such a step
+        // skips PH0-PH4: the actor_t and actor forwards run inside the
+        // quad phase below.  A launch's first step precomputed nothing
+        // (parameter slabs and the replay may change between launches) and
+        // takes PH0-PH4, as does every step at B > 64.
+        const bool pipe = otail && s > 0;
+        if (!pipe) {
+            // PH0: PER sample + batch gather (only on a launch's first
+            // step — at 64 < B <= 96 later steps were pre-sampled under
+            // the previous actor-Adam)
+            if (s == 0 || B > (PNWG - PNWG * 3 / 4) * 4) {
+                p_sample(g, 0, ep0 + s, bt0 + s, bs_cur);
+                p_bar(ctr, tgt);
+            }
+            PTIME(g, s, 1);
+            // PH1: four independent L1s (16 wgs each)
+            if (wg < PW4)
+                p_fwd(lds, g.bs2, nullptr, at.w1, at.b1, g.at_h1, B, O, 0,
+                      H, ACT_RELU, wg, PW4);
+            else if (wg < 2 * PW4)
                 p_fwd(lds, g.bs2, nullptr, ct.w1, ct.b1, g.ct_h1, B, O, 0,
                       H, ACT_RELU, wg - PW4, PW4);
-        } else if (wg < 3 * PW4) {
-            if (!otail || s == 0)
+            else if (wg < 3 * PW4)
                 p_fwd(lds, bs_cur, nullptr, c.w1, c.b1, g.c_h1, B, O, 0, H,
                       ACT_RELU, wg - 2 * PW4, PW4);
-        } else
-            p_fwd(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
-                  ACT_RELU, wg - 3 * PW4, PW4);
-        p_bar(ctr, tgt); PTIME(g, s, 2);
-        // PH2: actor_t.L2 | critic.L2(cat h1, a) | actor.L2
-        if (wg < PW3A)
-            p_fwd(lds, g.at_h1, nullptr, at.w2, at.b2, g.at_h2, B, H, 0, H,
-                  ACT_NONE, wg, PW3A);
-        else if (wg < 2 * PW3A)
-            p_fwd(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A, H,
-                  ACT_RELU, wg - PW3A, PW3A);
-        else
-            p_fwd(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0, H,
-                  ACT_NONE, wg - 2 * PW3A, PW3B);
-        p_bar(ctr, tgt); PTIME(g, s, 3);
-        // PH3: L3s
-        if (wg < PW3A)
-            p_fwd(lds, g.at_h2, nullptr, at.w3, at.b3, g.at_h3, B, H, 0, H,
-                  ACT_RELU, wg, PW3A);
-        else if (wg < 2 * PW3A)
-            p_fwd(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H, 0, H,
-                  ACT_RELU, wg - PW3A, PW3A);
-        else
-            p_fwd(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0, H,
-                  ACT_RELU, wg - 2 * PW3A, PW3B);
-        p_bar(ctr, tgt); PTIME(g, s, 4);
-        // PH4: heads — actor_t tanh -> a2 | critic softmax -> q |
-        //      actor tanh -> a_out
-        if (wg < PW3A)
-            p_fwd(lds, g.at_h3, nullptr, at.w4, at.b4, g.a2, B, H, 0, A,
-                  ACT_TANH, wg, PW3A);
-        else if (wg < 2 * PW3A)
-            p_fwd(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0, K,
-                  ACT_SOFTMAX, wg - PW3A, PW3A);
-        else
-            p_fwd(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0, A,
-                  ACT_TANH, wg - 2 * PW3A, PW3B);
-        // per-step loss accumulators zeroed here (grid barrier below
-        // orders this before the quad-chained proj-CE / pgrad adds)
-        if (wg == PNWG - 1 && threadIdx.x == 0) {
-            g.cnt->loss_critic = 0.f;
-            g.cnt->loss_actor = 0.f;
+            else
+                p_fwd(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
+                      ACT_RELU, wg - 3 * PW4, PW4);
+            p_bar(ctr, tgt); PTIME(g, s, 2);
+            // PH2: actor_t.L2 | critic.L2(cat h1, a) | actor.L2
+            if (wg < PW3A)
+                p_fwd(lds, g.at_h1, nullptr, at.w2, at.b2, g.at_h2, B, H, 0,
+                      H, ACT_NONE, wg, PW3A);
+            else if (wg < 2 * PW3A)
+                p_fwd(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A, H,
+                      ACT_RELU, wg - PW3A, PW3A);
+            else
+                p_fwd(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
+                      H, ACT_NONE, wg - 2 * PW3A, PW3B);
+            p_bar(ctr, tgt); PTIME(g, s, 3);
+            // PH3: L3s
+            if (wg < PW3A)
+                p_fwd(lds, g.at_h2, nullptr, at.w3, at.b3, g.at_h3, B, H, 0,
+                      H, ACT_RELU, wg, PW3A);
+            else if (wg < 2 * PW3A)
+                p_fwd(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H, 0, H,
+                      ACT_RELU, wg - PW3A, PW3A);
+            else
+                p_fwd(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
+                      H, ACT_RELU, wg - 2 * PW3A, PW3B);
+            p_bar(ctr, tgt); PTIME(g, s, 4);
+            // PH4: heads — actor_t tanh -> a2 | critic softmax -> q |
+            //      actor tanh -> a_out
+            if (wg < PW3A)
+                p_fwd(lds, g.at_h3, nullptr, at.w4, at.b4, g.a2, B, H, 0, A,
+                      ACT_TANH, wg, PW3A);
+            else if (wg < 2 * PW3A)
+                p_fwd(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0, K,
+                      ACT_SOFTMAX, wg - PW3A, PW3A);
+            else
+                p_fwd(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
+                      A, ACT_TANH, wg - 2 * PW3A, PW3B);
+            // per-step loss accumulators zeroed here (grid barrier below
+            // orders this before the quad-chained proj-CE / pgrad adds);
+            // a pipelined step's were zeroed in the previous step's PH27
+            if (wg == PNWG - 1 && threadIdx.x == 0) {
+                g.cnt->loss_critic = 0.f;
+                g.cnt->loss_actor = 0.f;
+            }
+            p_bar(ctr, tgt);
+        } else {
+            PTIME(g, s, 1); PTIME(g, s, 2); PTIME(g, s, 3); PTIME(g, s, 4);
         }
-        p_bar(ctr, tgt); PTIME(g, s, 5);
+        PTIME(g, s, 5);
         // PH5-8 as ONE phase: the critic_target chain + projection + CE is
         // ROW-LOCAL (row b's p_t depends only on row b's ct_h1/a2), so each
         // quad of 4 wgs walks its 4-row group through ct.L2 -> ct.L3 ->
         // ct.L4 softmax -> C51 projection/CE with quad-local barriers; the
         // 16 quads never wait on each other (grid barriers cost ~3.3 us,
         // quad barriers well under 1 us, and straggler coupling is gone).
+        // On a pipelined step the phase also carries what PH1-PH4 still
+        // owe: actor_t's forward is row-local too, so each quad first
+        // walks its rows through at.L1 -> at.L2 -> at.L3 -> at.L4 (tanh ->
+        // a2), and beside the quads the 32 spare workgroups (the policy
+        // block's tail crew) run the actor forward a.L1..L4 -> a_out over
+        // the whole batch, crew barriers between the layers.  Both use the
+        // weights the previous step's PH27 made final.
         {
             int q = wg >> 2, m = wg & 3;
             unsigned long long* qc = ctr + 192 + (q << 4);
+            if (pipe && wg >= QW && wg < QW + 32) {
+                p_fwd(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
+                      ACT_RELU, wg - QW, 32);
+                t_bar(ctr + 1280, trnd, 32);
+                p_fwd(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
+                      H, ACT_NONE, wg - QW, 32);
+                t_bar(ctr + 1280, trnd, 32);
+                p_fwd(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
+                      H, ACT_RELU, wg - QW, 32);
+                t_bar(ctr + 1280, trnd, 32);
+                p_fwd(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
+                      A, ACT_TANH, wg - QW, 32);
+                PTIMEW(g, s, 53, QW);        // actor crew's end
+            }
             for (int rg = q; rg < (B + 3) / 4; rg += PNWG / 4) {
                 long r0 = (long)rg * 4;
                 int nb = min(4, B - (int)r0);
+                if (pipe) {
+                    p_fwd(lds, g.bs2 + r0 * O, nullptr, at.w1, at.b1,
+                          g.at_h1 + r0 * H, nb, O, 0, H, ACT_RELU, m, 4);
+                    q_bar(qc, qrnd);
+                    p_fwd(lds, g.at_h1 + r0 * H, nullptr, at.w2, at.b2,
+                          g.at_h2 + r0 * H, nb, H, 0, H, ACT_NONE, m, 4);
+                    q_bar(qc, qrnd);
+                    p_fwd(lds, g.at_h2 + r0 * H, nullptr, at.w3, at.b3,
+                          g.at_h3 + r0 * H, nb, H, 0, H, ACT_RELU, m, 4);
+                    q_bar(qc, qrnd);
+                    p_fwd(lds, g.at_h3 + r0 * H, nullptr, at.w4, at.b4,
+                          g.a2 + r0 * A, nb, H, 0, A, ACT_TANH, m, 4);
+                    q_bar(qc, qrnd); PTIME(g, s, 54);
+                }
                 p_fwd(lds, g.ct_h1 + r0 * H, g.a2 + r0 * A, ct.w2, ct.b2,
                       g.ct_h2 + r0 * H, nb, H, A, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd);
@@ -769,6 +841,7 @@ k_step_persistent(StepArgs g, int nsteps) {
                       g.p_t + r0 * K, nb, H, 0, K, ACT_SOFTMAX, m, 4);
                 if (m == 0)
                     p_project_ce(g, lds, (int)r0);
+                PTIME(g, s, 55);
                 // no trailing q_bar: row groups are independent and the
                 // closing grid barrier publishes everything
             }
@@ -780,6 +853,12 @@ k_step_persistent(StepArgs g, int nsteps) {
         {
             int q = wg >> 2, m = wg & 3;
             unsigned long long* qc = ctr + 192 + (q << 4);
+            // this step's PER write-back rides on the first spare
+            // workgroup (B <= 64): the priorities have been final since
+            // the CE row, nothing reads the trees before the tail crew's
+            // sample two grid barriers on, and the ~20 us single-workgroup
+            // job no longer heads the tail crew's serial chain
+            if (otail) p_per_update(g, QW);
             for (int rg = q; rg < (B + 3) / 4; rg += PNWG / 4) {
                 long r0 = (long)rg * 4;
                 int nb = min(4, B - (int)r0);
@@ -830,13 +909,13 @@ k_step_persistent(StepArgs g, int nsteps) {
             int q = wg >> 2, m = wg & 3;
             unsigned long long* qc = ctr + 192 + (q << 4);
             if (otail && wg >= QW && wg < QW + 32) {
-                // tail crew (32 spare wgs): this step's PER write-back,
-                // then the NEXT step's sample and its ct/c L1 forwards —
-                // all hidden under the ~70 us policy megachain.  Safe:
-                // bs2/ba/br/bd/bw/bidx of step s were fully consumed
+                // tail crew (32 spare wgs): the NEXT step's sample (the
+                // trees were repaired in the critic dX phase), its ct L1
+                // and its whole critic forward — hidden under the policy
+                // megachain.  It precomputes nothing on a launch's last
+                // step, so nothing precomputed crosses a launch boundary.
+                // Safe: bs2/ba/br/bd/bw/bidx of step s were fully consumed
                 // before this block; bs_nxt is the other bs buffer.
-                p_per_update(g, QW);
-                t_bar(ctr + 1280, trnd, 32);
                 if (s + 1 < nsteps) {
                     p_sample(g, QW, ep0 + s + 1, bt0 + s + 1, bs_nxt);
                     t_bar(ctr + 1280, trnd, 32);
@@ -844,7 +923,22 @@ k_step_persistent(StepArgs g, int nsteps) {
                           O, 0, H, ACT_RELU, wg - QW, 32);
                     p_fwd(lds, bs_nxt, nullptr, c.w1, c.b1, g.c_h1, B, O,
                           0, H, ACT_RELU, wg - QW, 32);
+                    // ... and the rest of the NEXT step's critic forward:
+                    // the critic's weights have been final since PH14,
+                    // ba is the next step's since the sample above, and
+                    // this step's last readers of c_h* and q (PH13, the
+                    // CE row) are long past
+                    t_bar(ctr + 1280, trnd, 32);
+                    p_fwd(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A,
+                          H, ACT_RELU, wg - QW, 32);
+                    t_bar(ctr + 1280, trnd, 32);
+                    p_fwd(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H,
+                          0, H, ACT_RELU, wg - QW, 32);
+                    t_bar(ctr + 1280, trnd, 32);
+                    p_fwd(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0,
+                          K, ACT_SOFTMAX, wg - QW, 32);
                 }
+                PTIMEW(g, s, 52, QW);        // tail crew's end
             }
             for (int rg = q; rg < (B + 3) / 4; rg += PNWG / 4) {
                 long r0 = (long)rg * 4;
@@ -911,7 +1005,7 @@ k_step_persistent(StepArgs g, int nsteps) {
                  g.g_actor + g.al[3].b_off, B, H, 0, A, wg - PNWG * 7 / 8,
                  PNWG - 2 - PNWG * 7 / 8);
         else if (!otail && wg == PNWG - 1)
-            p_per_update(g, PNWG - 1);   // tail crew did it when otail
+            p_per_update(g, PNWG - 1);   // PH10-12 did it when otail
         p_bar(ctr, tgt); PTIME(g, s, 26);
         // PH27: Adam + soft-update, actor (wgs 0-47) overlapped with the
         // NEXT step's PER sample + gather (wgs 48-63; tree was repaired in
@@ -924,6 +1018,14 @@ k_step_persistent(StepArgs g, int nsteps) {
                             ta0 + s, anw);
             else if (s + 1 < nsteps && B <= (PNWG - PNWG * 3 / 4) * 4)
                 p_sample(g, PNWG * 3 / 4, ep0 + s + 1, bt0 + s + 1, bs_nxt);
+            // the next step is pipelined and has no PH4: zero its loss
+            // accumulators here (this step's are complete; the barrier
+            // below orders the zeroes before the next proj-CE adds)
+            if (otail && s + 1 < nsteps && wg == PNWG - 1
+                && threadIdx.x == 0) {
+                g.cnt->loss_critic = 0.f;
+                g.cnt->loss_actor = 0.f;
+            }
         }
         p_bar(ctr, tgt); PTIME(g, s, 27); PTIME(g, s, 28);
         // (the per-step schedule-counter tick phase is gone: counters were

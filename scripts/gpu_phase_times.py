@@ -1,5 +1,12 @@
 #!/usr/bin/env python3
-"""Print per-phase times of the persistent step kernel (100 MHz clock)."""
+"""Print per-phase times of the persistent step kernel (100 MHz clock).
+
+The kernel stamps step 1 of a multi-step launch: the first step that runs
+the steady-state schedule (the tail crew's precompute under the previous
+policy block, the merged forward phase).  Step 0 of a launch runs the
+un-pipelined PH0-PH4 schedule instead; `--first` stamps that one through
+one-step launches.
+"""
 
 import os
 import sys
@@ -8,25 +15,43 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from scripts.gpu_microbench import make_engine  # noqa: E402
 
-# stamp map after the round-2 quad restructure: fused regions stamp all
-# their legacy indices back-to-back, so collapsed rows read ~0 us and the
-# preceding row carries the whole block
+# stamp map: fused regions stamp all their legacy indices back-to-back, so
+# collapsed rows read ~0 us and the preceding row carries the whole block.
+# On a steady-state step PH0-PH4 are collapsed too: the critic forward ran
+# under the previous policy block, and the "fwd" row is the merged phase
+# (quads: actor_t chain -> critic_target chain -> projection + CE; crew:
+# actor forward).
 PHASES = [
     "PH0 sample", "PH1 L1x4", "PH2 L2x3", "PH3 L3x3", "PH4 headsx3",
-    "quadA ct+proj", "(fused)", "(fused)", "(fused)",
+    "fwd quads+crew", "(fused)", "(fused)", "(fused)",
     "quadB c.dX", "(fused)", "(fused)", "c.dW", "c.adam",
     "quadC policy+tail", "(fused)", "(fused)", "(fused)", "(fused)",
     "(fused)", "(fused)", "(fused)", "(fused)", "(fused)",
     "(fused)", "a.dW", "a.adam", "(fused)",
 ]
+# stamps inside a phase, us after the stamp that opens it:
+# (label, slot, opening slot)
+INNER = [
+    ("fwd: quad 0 a2 ready", 54, 5),
+    ("fwd: quad 0 end", 55, 5),
+    ("fwd: actor crew end", 53, 5),
+    ("policy: quad 0 end", 51, 14),
+    ("policy: tail crew end", 52, 14),
+]
 
+first = "--first" in sys.argv[1:]
 eng = make_engine()
-eng.step(50)          # warm; stamps overwritten each launch (s==0 only)
+eng.step(50)          # warm; stamps overwritten each launch
+if first:
+    eng.step(1)
 ts = eng.read("tstamp").numpy()
-t0 = ts[0]
 total = 0.0
 for i, name in enumerate(PHASES):
     dt_us = (ts[i + 1] - ts[i]) / 100.0   # 100 MHz -> us
     total += dt_us
-    print(f"{name:14s} {dt_us:8.2f} us")
-print(f"{'TOTAL':14s} {total:8.2f} us (stamped step 0 incl. barriers)")
+    print(f"{name:18s} {dt_us:8.2f} us")
+print(f"{'TOTAL':18s} {total:8.2f} us (stamped step "
+      f"{'0 of a one-step launch' if first else '1 of 50'}, incl. barriers)")
+for name, slot, base in INNER:
+    if ts[slot] > ts[base]:               # not stamped on this schedule
+        print(f"{name:24s} +{(ts[slot] - ts[base]) / 100.0:7.2f} us")
