@@ -205,3 +205,128 @@ class VectorGoalReach:
         """(ep_pos, ep_act, len, succ, goal) of the episode so far."""
         return (self.ep_pos, self.ep_act, self.len.copy(), self.succ.copy(),
                 self.goal.copy())
+
+
+# seed-xor constant of the device process-noise stream (engine_synth.hip
+# k_syn_tick)
+SYNTH_PROC_STREAM = 0x51A7E
+
+
+class GeneratorProcNoise:
+    """Process-noise source of VectorSynthetic backed by a numpy
+    Generator (the default)."""
+
+    def __init__(self, rng: np.random.Generator):
+        self.rng = rng
+
+    def reset(self):
+        pass
+
+    def draw(self, tick: int, n_envs: int, obs_dim: int) -> np.ndarray:
+        return self.rng.standard_normal((n_envs, obs_dim))
+
+
+class PhiloxProcNoise:
+    """Process-noise source drawing what the device synthetic rollout
+    draws (the role PhiloxHerRng plays for HER): the standard normal of dim
+    k of env i at `tick` of rollout episode `episode` is the Box-Muller of
+    the first two philox words keyed by (seed ^ SYNTH_PROC_STREAM,
+    (episode << 20) | (tick + 2), (k << 32) | i).  The uniforms are the
+    kernel's float32 (0, 1] map; the transcendental part is float64.
+    ``reset()`` moves on to the next episode, as the device epoch does."""
+
+    def __init__(self, seed: int, episode: int = 0):
+        self.seed, self.episode = int(seed), int(episode)
+
+    def reset(self):
+        self.episode += 1
+
+    @staticmethod
+    def _u01(x: int) -> np.float32:
+        return np.float32(np.float32(np.float32(np.uint32(x))
+                                     + np.float32(1.0))
+                          * np.float32(2.3283064e-10))
+
+    def normal(self, tick: int, env: int, dim: int) -> float:
+        from ..her import philox4x32_10
+        w = philox4x32_10(self.seed ^ SYNTH_PROC_STREAM,
+                          (self.episode << 20) | (int(tick) + 2),
+                          (int(dim) << 32) | int(env))
+        u1 = max(float(self._u01(w[0])), 1e-12)
+        u2 = float(self._u01(w[1]))
+        return float(np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2))
+
+    def draw(self, tick: int, n_envs: int, obs_dim: int) -> np.ndarray:
+        return np.array([[self.normal(tick, i, k) for k in range(obs_dim)]
+                         for i in range(n_envs)])
+
+
+class VectorSynthetic:
+    """M independent SyntheticEnv instances of one spec in float32 numpy
+    arrays: s' = tanh(s.W + a.U + proc_sigma.N(0,1)), r = -mean(s'^2) +
+    0.1.mean(a^2), fixed horizon.  Takes SyntheticEnv's (obs_dim, act_dim,
+    horizon, act_high, seed) and derives W, U with the same default_rng(seed)
+    draws, so one seed names one env on both sides; they are exposed as
+    float32.  Actions are NORMALIZED to (-1, 1) and scaled by act_high
+    inside (the NormalizeAction convention), as in VectorPendulum, and
+    episodes are synchronized: done is the scalar horizon flag.
+
+    Host twin of the device synthetic rollout (ops/hip/engine_synth.hip),
+    so it serves both as the CPU vector-actor path and as the parity oracle.
+    The process noise comes from ``proc_noise``, a replaceable source with
+    ``draw(tick, n_envs, obs_dim)`` and ``reset()``: a GeneratorProcNoise by
+    default, a PhiloxProcNoise to draw what the kernel draws.  ``seed``
+    names the env (W, U); reset states and the default process noise come
+    from a Generator seeded with ``noise_seed`` (``seed`` when None, as in
+    SyntheticEnv), so a caller that seeds other streams with ``seed`` can
+    keep this one apart."""
+
+    def __init__(self, n_envs: int, obs_dim: int, act_dim: int,
+                 horizon: int = 1000, act_high: float = 1.0,
+                 seed: int | None = None, proc_sigma: float = 0.01,
+                 proc_noise=None, noise_seed: int | None = None):
+        self.n = int(n_envs)
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.horizon = int(horizon)
+        self.act_high = np.float32(act_high)
+        self.proc_sigma = np.float32(proc_sigma)
+        self.rng = np.random.default_rng(
+            seed if noise_seed is None else noise_seed)
+        mix_rng = np.random.default_rng(0 if seed is None else seed)
+        a = (mix_rng.standard_normal((self.obs_dim, self.obs_dim))
+             / np.sqrt(self.obs_dim))
+        self.W = (0.9 * a).astype(np.float32)
+        self.U = (mix_rng.standard_normal((self.act_dim, self.obs_dim))
+                  / np.sqrt(self.act_dim)).astype(np.float32)
+        self.proc_noise = (GeneratorProcNoise(self.rng) if proc_noise is None
+                           else proc_noise)
+        self.state = np.zeros((self.n, self.obs_dim), np.float32)
+        self.t = 0
+
+    def set_state(self, state) -> np.ndarray:
+        """Start an episode from the given states."""
+        self.state = np.array(state, np.float32).reshape(self.n,
+                                                         self.obs_dim)
+        self.t = 0
+        return self.state.copy()
+
+    def reset(self) -> np.ndarray:
+        self.proc_noise.reset()
+        return self.set_state(
+            0.1 * self.rng.standard_normal((self.n, self.obs_dim)))
+
+    def step(self, actions: np.ndarray):
+        """actions [M, act_dim] in (-1, 1).  Returns (obs, rewards, done)
+        where done is a scalar — the synchronized horizon flag."""
+        f = np.float32
+        u = np.clip(np.asarray(actions, f).reshape(self.n, self.act_dim),
+                    f(-1.0), f(1.0)) * self.act_high
+        z = self.state @ self.W + u @ self.U
+        if self.proc_sigma != 0:
+            noise = self.proc_noise.draw(self.t, self.n, self.obs_dim)
+            z = z + self.proc_sigma * np.asarray(noise).astype(f)
+        self.state = np.tanh(z).astype(f)
+        reward = (-np.mean(self.state ** 2, axis=1)
+                  + f(0.1) * np.mean(u ** 2, axis=1)).astype(f)
+        self.t += 1
+        return self.state.copy(), reward, self.t >= self.horizon

@@ -384,6 +384,39 @@ class FusedEngine:
         succ [M] (steps past an env's len are stale)."""
         return dict(self.ext.goal_rollout_episode(self.h))
 
+    # -- GPU-resident synthetic-spec rollout, any (obs, act): device
+    # SyntheticEnv dynamics + noise + n-step fold, rows written straight
+    # into this engine's on-HBM replay; see ops/hip/engine_synth.hip --
+    def synth_rollout_alloc(self, n_envs, n_steps, W, U, horizon=1000,
+                            gamma=0.99, act_high=1.0, proc_sigma=0.01,
+                            noise="gaussian", eps=0.3, ou_theta=0.15,
+                            ou_sigma=0.2, ou_mu=0.0, seed=0):
+        """W [obs, obs] and U [act, obs] are the env's mixing matrices
+        (SyntheticEnv.W / .U, VectorSynthetic.W / .U)."""
+        kind = {"gaussian": 0, "ou": 1}[noise]
+        self.ext.synth_rollout_alloc(
+            self.h, int(n_envs), int(n_steps), int(horizon), float(gamma),
+            float(act_high), float(proc_sigma), kind, float(eps),
+            float(ou_theta), float(ou_sigma), float(ou_mu), int(seed),
+            torch.as_tensor(np.asarray(W, np.float32)),
+            torch.as_tensor(np.asarray(U, np.float32)))
+
+    def synth_rollout_run(self, episodes=1, reset=True, use_graph=True):
+        """Run whole episodes on-device (one hipGraph per episode when
+        reset=True); returns (env_steps, transitions_emitted)."""
+        self.ext.synth_rollout_run(self.h, int(episodes), bool(reset),
+                                   bool(use_graph))
+        info = self.ext.synth_rollout_info(self.h)
+        return (episodes * info["env_steps_per_episode"],
+                episodes * info["emits_per_episode"])
+
+    def synth_rollout_set_state(self, state):
+        self.ext.synth_rollout_set_state(
+            self.h, torch.as_tensor(np.asarray(state, np.float32)))
+
+    def synth_rollout_info(self):
+        return self.ext.synth_rollout_info(self.h)
+
     def rollout_last_rows(self):
         """Host copy of the rows of the LAST rollout episode only, in write
         order, from its replay base and row count (replay_rows() returns

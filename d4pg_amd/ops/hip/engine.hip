@@ -29,6 +29,7 @@
 #include "engine_rowblock.hip"
 #include "engine_rollout.hip"
 #include "engine_goal.hip"
+#include "engine_synth.hip"
 #include "engine_mfma.hip"
 #include "engine_persistent.hip"
 
@@ -840,7 +841,7 @@ public:
     hipGraphExec_t roll_graph_exec = nullptr;
     int roll_emits_per_ep = 0;
     // which producer owns roll_pool_ and the episode graph
-    enum { ROLL_NONE = 0, ROLL_PENDULUM = 1, ROLL_GOAL = 2 };
+    enum { ROLL_NONE = 0, ROLL_PENDULUM = 1, ROLL_GOAL = 2, ROLL_SYNTH = 3 };
     int roll_kind_ = ROLL_NONE;
 
     void rollout_free() {
@@ -1147,6 +1148,163 @@ public:
         HIP_CHECK(hipMemcpy(goal_.len, zero.data(), M * 4,
                             hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(goal_.succ, zero.data(), M * 4,
+                            hipMemcpyHostToDevice));
+    }
+
+    // ---------------- GPU-resident synthetic-spec rollout (engine_synth.hip)
+    // Any (obs, act).  Shares the pool pointer, the hidden buffers, the
+    // policy chain, the episode graph and rollout_free() with the other two
+    // rollouts; one is allocated at a time (roll_kind_).  The env's mixing
+    // matrices live in the pool as one layer slab ([W; U] is already
+    // [in][out], plus a zero bias), so the mixing GEMM is a plain forward
+    // job with a concat input.
+    SynRollArgs syn_{};
+    float* syn_dyn_ = nullptr;
+    LayerDesc syn_dyn_desc_{};
+    int syn_emits_per_ep = 0;
+
+    void synth_rollout_alloc(int M, int nsteps, int horizon, float gamma,
+                             float act_high, float proc_sigma,
+                             int noise_kind, float eps, float ou_theta,
+                             float ou_sigma, float ou_mu, uint64_t seed,
+                             const float* W, const float* U) {
+        const int O = cfg.obs, A = cfg.act, H = cfg.hidden;
+        if (O + A > FWD_XMAX)
+            throw std::runtime_error(
+                "synth rollout: obs + act exceeds FWD_XMAX LDS tile");
+        if (M < 1)
+            throw std::runtime_error("synth rollout: n_envs < 1");
+        if (nsteps < 1 || horizon < nsteps)
+            throw std::runtime_error("synth rollout horizon < n_steps");
+        if (horizon >= (1 << 20) - 2)
+            throw std::runtime_error("synth rollout horizon >= 2^20 - 2");
+        if (cfg.capacity < (long)M * (horizon - nsteps + 1))
+            throw std::runtime_error(
+                "synth rollout: replay capacity below one episode's "
+                "M*(horizon-n+1) rows (two rows of one episode would share "
+                "a slot)");
+        rollout_free();
+        SynRollArgs a{};
+        a.M = M; a.O = O; a.A = A; a.n = nsteps; a.horizon = horizon;
+        a.gamma = gamma; a.eps = eps; a.ou_theta = ou_theta;
+        a.ou_sigma = ou_sigma; a.ou_mu = ou_mu; a.ou_dt = 1e-2f;
+        a.act_high = act_high; a.proc_sigma = proc_sigma;
+        a.noise_kind = noise_kind; a.seed = seed;
+        a.per_alpha = cfg.per_alpha;
+        long off = 0;
+        auto sub = [&](long nelem) {            // nelem 4-byte words
+            long o = off;
+            off += (nelem * 4 + 255) & ~255L;
+            return o;
+        };
+        const long MO = (long)M * O, MA = (long)M * A;
+        const long n_dyn = (long)(O + A) * O;
+        long o_obs = sub(MO), o_act = sub(MA), o_env = sub(MA), o_z = sub(MO),
+             o_ou = sub(MA), o_sr = sub(nsteps * MO), o_ar = sub(nsteps * MA),
+             o_rr = sub((long)nsteps * M), o_ep = sub(4),
+             o_dyn = sub(n_dyn + O),
+             o_h1 = sub((long)M * H), o_h2 = sub((long)M * H),
+             o_h3 = sub((long)M * H);
+        HIP_CHECK(hipMalloc(&roll_pool_, off));
+        HIP_CHECK(hipMemset(roll_pool_, 0, off));
+        char* base = (char*)roll_pool_;
+        a.obs = (float*)(base + o_obs); a.act = (float*)(base + o_act);
+        a.act_env = (float*)(base + o_env); a.z = (float*)(base + o_z);
+        a.ou_x = (float*)(base + o_ou);
+        a.s_ring = (float*)(base + o_sr); a.a_ring = (float*)(base + o_ar);
+        a.r_ring = (float*)(base + o_rr);
+        a.ep_state = (long long*)(base + o_ep);
+        syn_dyn_ = (float*)(base + o_dyn);
+        r_h1 = (float*)(base + o_h1); r_h2 = (float*)(base + o_h2);
+        r_h3 = (float*)(base + o_h3);
+        // [W; U] then the zero bias the memset left
+        HIP_CHECK(hipMemcpy(syn_dyn_, W, (long)O * O * 4,
+                            hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(syn_dyn_ + (long)O * O, U, (long)A * O * 4,
+                            hipMemcpyHostToDevice));
+        // the episode kernels run on the engine's non-blocking stream
+        HIP_CHECK(hipDeviceSynchronize());
+        syn_dyn_desc_ = LayerDesc{O, A, O, 0, n_dyn};
+        a.rs = ws.rs; a.ra = ws.ra; a.rr = ws.rr; a.rs2 = ws.rs2; a.rd = ws.rd;
+        a.sum_tree = ws.sum_tree; a.min_tree = ws.min_tree;
+        a.tree_cap = ws.tree_cap; a.capacity = cfg.capacity;
+        a.cnt = ws.cnt;
+        syn_ = a;
+        syn_emits_per_ep = horizon - nsteps + 1;
+        roll_kind_ = ROLL_SYNTH;
+    }
+
+    void synth_enqueue_episode(bool reset) {
+        SynRollArgs& a = syn_;
+        const long elems = (long)a.M * (a.O > a.A ? a.O : a.A);
+        int wgs = ceil_div(elems, 256);
+        if (wgs > 2048) wgs = 2048;
+        // one wave per env, four to a workgroup
+        int twgs = ceil_div(a.M, 4);
+        if (twgs > 2048) twgs = 2048;
+        hipLaunchKernelGGL(k_syn_begin, dim3(1), dim3(64), 0, stream, a);
+        if (reset)
+            hipLaunchKernelGGL(k_syn_reset, dim3(wgs), dim3(256), 0, stream,
+                               a);
+        FwdJob mix = fwd_job(a.obs, a.act_env, syn_dyn_, syn_dyn_desc_, a.z,
+                             ACT_NONE, a.M);
+        int emit_k = 0;
+        for (int t = 0; t < a.horizon; ++t) {
+            roll_fwd_chain(a.obs, a.act, a.M);
+            int slot = t % a.n;
+            hipLaunchKernelGGL(k_syn_act, dim3(wgs), dim3(256), 0, stream, a,
+                               t, slot);
+            if (fwd_uses_mfma(a.M)) launch_fwd_mfma(mix);
+            else launch_fwd_valu(mix);
+            int ek = (t >= a.n - 1) ? emit_k : -1;
+            int done = (t == a.horizon - 1) ? 1 : 0;
+            hipLaunchKernelGGL(k_syn_tick, dim3(twgs), dim3(256), 0, stream,
+                               a, t, slot, ek, done);
+            if (ek >= 0) ++emit_k;
+        }
+        hipLaunchKernelGGL(k_syn_end, dim3(1), dim3(64), 0, stream, a,
+                           (long)emit_k * a.M);
+        launch_tree_rebuild(1024);              // no-op on uniform replay
+    }
+
+    void synth_rollout_run(int episodes, bool reset, bool use_graph) {
+        if (roll_kind_ != ROLL_SYNTH)
+            throw std::runtime_error("synth_rollout_alloc first");
+        if (use_graph && reset) {
+            if (!roll_graph_exec) {
+                HIP_CHECK(hipStreamBeginCapture(
+                    stream, hipStreamCaptureModeThreadLocal));
+                synth_enqueue_episode(true);
+                HIP_CHECK(hipStreamEndCapture(stream, &roll_graph));
+                HIP_CHECK(hipGraphInstantiate(&roll_graph_exec, roll_graph,
+                                              nullptr, nullptr, 0));
+            }
+            for (int e = 0; e < episodes; ++e)
+                HIP_CHECK(hipGraphLaunch(roll_graph_exec, stream));
+        } else {
+            for (int e = 0; e < episodes; ++e)
+                synth_enqueue_episode(reset);
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+
+    // the per-episode device words: [0] philox epoch, [1] replay base
+    void synth_rollout_words(long long (&w)[2]) {
+        if (roll_kind_ != ROLL_SYNTH)
+            throw std::runtime_error("synth_rollout_alloc first");
+        HIP_CHECK(hipMemcpy(w, syn_.ep_state, sizeof(w),
+                            hipMemcpyDeviceToHost));
+    }
+
+    // test hook: inject exact env state, leaving the OU process as
+    // k_syn_reset leaves it
+    void synth_rollout_set_state(const float* state, int M) {
+        if (roll_kind_ != ROLL_SYNTH || M != syn_.M)
+            throw std::runtime_error("synth_rollout_set_state: bad M");
+        HIP_CHECK(hipMemcpy(syn_.obs, state, (long)M * syn_.O * 4,
+                            hipMemcpyHostToDevice));
+        std::vector<float> ou((long)M * syn_.A, syn_.ou_mu);
+        HIP_CHECK(hipMemcpy(syn_.ou_x, ou.data(), ou.size() * 4,
                             hipMemcpyHostToDevice));
     }
 

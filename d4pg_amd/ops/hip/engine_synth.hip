@@ -1,0 +1,188 @@
+// Device rollout of the synthetic-spec envs, for any (obs, act): M vectorized
+// SyntheticEnv instances (s' = tanh(s.W + a.U + sigma.N(0,1)), r = -mean(s'^2)
+// + 0.1.mean(a^2), fixed horizon), exploration noise and the n-step fold,
+// writing rows straight into the on-HBM replay.  Used by
+// Engine::synth_rollout_*.  Host twin and parity oracle: VectorSynthetic +
+// VecNStep (d4pg_amd/envs/vector.py).
+//
+// Episodes are synchronized (all M envs end at the horizon), as for Pendulum,
+// so the emit pattern is static and k_roll_tick's ring fold carries over with
+// general strides.  Per tick: the policy chain obs -> act, k_syn_act (noise,
+// clip, ring write), the mixing GEMM z = [obs ‖ act_env] . [W; U] through the
+// engine's own forward kernels, then k_syn_tick (process noise, tanh, reward,
+// fold and emit).
+//
+// Philox keys of the rollout streams (seed ^ constant; ctr_hi = (episode <<
+// 20) | sub-stream, ctr_lo = (dim << 32) | env):
+//   0xD011E  reset state          sub-stream 1          (all rollouts)
+//   0x2F01E  exploration noise    sub-stream tick + 2   (all rollouts)
+//   0x4E12E  HER draw             sub-stream t          (goal rollout)
+//   0x51A7E  process noise        sub-stream tick + 2   (this file)
+
+namespace d4pg {
+
+struct SynRollArgs {
+    int M, O, A, n, horizon;
+    float gamma, eps, ou_theta, ou_sigma, ou_mu, ou_dt;
+    float act_high, proc_sigma;
+    int noise_kind;                    // 0 = gaussian, 1 = OU
+    uint64_t seed;
+    float per_alpha;
+    // env + noise state: obs [M][O] (the env state IS the observation),
+    // act [M][A] policy output, act_env [M][A] = clipped noisy action *
+    // act_high, z [M][O] mixing GEMM output, ou_x [M][A]
+    float *obs, *act, *act_env, *z, *ou_x;
+    // n-step rings: s_ring [n][M][O], a_ring [n][M][A], r_ring [n][M]
+    float *s_ring, *a_ring, *r_ring;
+    // per-episode device state: [0] philox epoch, [1] replay base pos
+    long long* ep_state;
+    // replay
+    float *rs, *ra, *rr, *rs2, *rd;
+    double *sum_tree, *min_tree;
+    long tree_cap, capacity;
+    Counters* cnt;
+};
+
+// episode prologue: bump the philox epoch, latch the replay write base
+__global__ void k_syn_begin(SynRollArgs a) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        a.ep_state[0] += 1;
+        a.ep_state[1] = a.cnt->pos;
+    }
+}
+
+// reset all M envs: state 0.1 * N(0,1) per dim (SyntheticEnv._reset), OU
+// state to mu
+__global__ void k_syn_reset(SynRollArgs a) {
+    const long long ep = a.ep_state[0];
+    const int O = a.O;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long e = t0; e < (long)a.M * O; e += stride) {
+        const int i = (int)(e / O), k = (int)(e % O);
+        Philox4 r = philox4(a.seed ^ 0xD011Eull, ((uint64_t)ep << 20) | 1u,
+                            ((uint64_t)k << 32) | (uint64_t)i);
+        a.obs[e] = 0.1f * n01(r.v[0], r.v[1]);
+    }
+    for (long e = t0; e < (long)a.M * a.A; e += stride) a.ou_x[e] = a.ou_mu;
+}
+
+// after the policy forward: exploration noise as k_goal_tick draws it ->
+// clip -> the NORMALIZED action into the ring, the scaled one to the env;
+// s_t into the ring before the env steps.  eps == 0 skips the Gaussian
+// draw; the OU state advances whatever eps is (it is state, and eps only
+// scales what is added), as in the other two rollouts.
+__global__ void k_syn_act(SynRollArgs a, int tick, int slot) {
+    const long long ep = a.ep_state[0];
+    const int M = a.M, O = a.O, A = a.A;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long e = t0; e < (long)M * A; e += stride) {
+        const int i = (int)(e / A), k = (int)(e % A);
+        float u = a.act[e];                // policy output, tanh in (-1,1)
+        if (a.noise_kind == 0 && a.eps != 0.0f) {
+            Philox4 r = philox4(a.seed ^ 0x2F01Eull,
+                                ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
+                                ((uint64_t)k << 32) | (uint64_t)i);
+            u += a.eps * n01(r.v[0], r.v[1]);
+        } else if (a.noise_kind == 1) {
+            Philox4 r = philox4(a.seed ^ 0x2F01Eull,
+                                ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
+                                ((uint64_t)k << 32) | (uint64_t)i);
+            float x = a.ou_x[e];
+            x += a.ou_theta * (a.ou_mu - x) * a.ou_dt
+                 + a.ou_sigma * sqrtf(a.ou_dt) * n01(r.v[0], r.v[1]);
+            a.ou_x[e] = x;
+            u += a.eps * x;
+        }
+        u = fminf(fmaxf(u, -1.0f), 1.0f);
+        a.a_ring[(long)slot * M * A + e] = u;
+        a.act_env[e] = u * a.act_high;
+    }
+    for (long e = t0; e < (long)M * O; e += stride)
+        a.s_ring[(long)slot * M * O + e] = a.obs[e];
+}
+
+// one synchronized tick after the mixing GEMM: one wave per env, lanes
+// striding over the dims (k = lane, lane + 64, ...) so every O-wide row
+// access is coalesced.  Process noise -> tanh -> reward (two wave sums) ->
+// ring write -> (optional) matured-transition emit into the replay.
+// slot/emit_k/done are per-tick constants baked into the episode graph.
+__global__ __launch_bounds__(256)
+void k_syn_tick(SynRollArgs a, int tick, int slot, int emit_k, int done) {
+    const int lane = threadIdx.x & 63;
+    const int wpb = blockDim.x >> 6;
+    const long long ep = a.ep_state[0], base = a.ep_state[1];
+    const double pa = (emit_k >= 0 && a.sum_tree)
+        ? per_leaf_value(a.cnt->max_priority, a.per_alpha) : 0.0;
+    const int M = a.M, O = a.O, A = a.A, n = a.n;
+    const int start = (slot + 1) % n;           // oldest ring entry
+    for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < M;
+         i += gridDim.x * wpb) {
+        const long dst = emit_k >= 0
+            ? (long)((base + (long long)emit_k * M + i) % a.capacity) : 0;
+
+        // --- SyntheticEnv._step: s' = tanh(z + sigma * N(0,1)) ---
+        float ss = 0.0f;
+        for (int k = lane; k < O; k += 64) {
+            float zz = a.z[(long)i * O + k];
+            if (a.proc_sigma != 0.0f) {
+                Philox4 r = philox4(a.seed ^ 0x51A7Eull,
+                                    ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
+                                    ((uint64_t)k << 32) | (uint64_t)i);
+                zz += a.proc_sigma * n01(r.v[0], r.v[1]);
+            }
+            const float s2 = tanhf(zz);
+            a.obs[(long)i * O + k] = s2;
+            if (emit_k >= 0) a.rs2[dst * O + k] = s2;
+            ss += s2 * s2;
+        }
+        float sa = 0.0f;
+        for (int k = lane; k < A; k += 64) {
+            const float u = a.act_env[(long)i * A + k];
+            sa += u * u;
+        }
+        for (int s = 32; s > 0; s >>= 1) {
+            ss += __shfl_xor(ss, s, 64);
+            sa += __shfl_xor(sa, s, 64);
+        }
+        const float r = -ss / (float)O + 0.1f * sa / (float)A;
+        if (lane == 0) a.r_ring[(long)slot * M + i] = r;
+
+        // --- matured n-step emit (VecNStep parity): transition
+        // (s_{t-n+1}, a_{t-n+1}, sum gamma^k r, s_{t+1}, done); the ring's
+        // newest entry is this tick's r, still in a register ---
+        if (emit_k >= 0) {
+            const float* s0 = a.s_ring + ((long)start * M + i) * O;
+            const float* a0 = a.a_ring + ((long)start * M + i) * A;
+            for (int k = lane; k < O; k += 64) a.rs[dst * O + k] = s0[k];
+            for (int k = lane; k < A; k += 64) a.ra[dst * A + k] = a0[k];
+            if (lane == 0) {
+                float R = 0.0f, gk = 1.0f;
+                for (int k = 0; k < n - 1; ++k) {
+                    R += gk * a.r_ring[(long)((start + k) % n) * M + i];
+                    gk *= a.gamma;
+                }
+                R += gk * r;
+                a.rr[dst] = R;
+                a.rd[dst] = (float)done;
+                if (a.sum_tree) {               // null: uniform replay
+                    a.sum_tree[a.tree_cap + dst] = pa;
+                    a.min_tree[a.tree_cap + dst] = pa;
+                }
+            }
+        }
+    }
+}
+
+// episode epilogue: advance the replay counters by the emitted block
+__global__ void k_syn_end(SynRollArgs a, long emitted) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        long long base = a.ep_state[1];
+        a.cnt->pos = (base + emitted) % a.capacity;
+        long long sz = a.cnt->size + emitted;
+        a.cnt->size = sz > a.capacity ? a.capacity : sz;
+    }
+}
+
+}  // namespace d4pg

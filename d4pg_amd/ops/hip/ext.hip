@@ -387,6 +387,58 @@ static py::dict goal_rollout_episode(int64_t h) {
     return d;
 }
 
+// ---- GPU-resident synthetic-spec rollout (engine_synth.hip) ----
+static void synth_rollout_alloc(int64_t h, int64_t M, int64_t n_steps,
+                                int64_t horizon, double gamma,
+                                double act_high, double proc_sigma,
+                                int64_t noise_kind, double eps,
+                                double ou_theta, double ou_sigma,
+                                double ou_mu, int64_t seed, torch::Tensor W,
+                                torch::Tensor U) {
+    Engine& e = get(h);
+    auto tw = f32_contig(W), tu = f32_contig(U);
+    const int64_t O = e.cfg.obs, A = e.cfg.act;
+    if (tw.dim() != 2 || tw.size(0) != O || tw.size(1) != O)
+        throw std::runtime_error("synth rollout: W is not [obs][obs]");
+    if (tu.dim() != 2 || tu.size(0) != A || tu.size(1) != O)
+        throw std::runtime_error("synth rollout: U is not [act][obs]");
+    e.synth_rollout_alloc((int)M, (int)n_steps, (int)horizon, (float)gamma,
+                          (float)act_high, (float)proc_sigma,
+                          (int)noise_kind, (float)eps, (float)ou_theta,
+                          (float)ou_sigma, (float)ou_mu, (uint64_t)seed,
+                          tw.data_ptr<float>(), tu.data_ptr<float>());
+}
+
+static void synth_rollout_run(int64_t h, int64_t episodes, bool reset,
+                              bool use_graph) {
+    get(h).synth_rollout_run((int)episodes, reset, use_graph);
+}
+
+static void synth_rollout_set_state(int64_t h, torch::Tensor state) {
+    Engine& e = get(h);
+    auto t = f32_contig(state);
+    TORCH_CHECK(t.numel() % e.cfg.obs == 0, "state is not [M, obs]");
+    e.synth_rollout_set_state(t.data_ptr<float>(),
+                              (int)(t.numel() / e.cfg.obs));
+}
+
+static py::dict synth_rollout_info(int64_t h) {
+    Engine& e = get(h);
+    long long w[2];
+    e.synth_rollout_words(w);           // throws unless a synth rollout is up
+    py::dict d;
+    d["M"] = e.syn_.M;
+    d["O"] = e.syn_.O;
+    d["A"] = e.syn_.A;
+    d["n"] = e.syn_.n;
+    d["horizon"] = e.syn_.horizon;
+    d["emits_per_episode"] = (long)e.syn_emits_per_ep * e.syn_.M;
+    d["env_steps_per_episode"] = (long)e.syn_.horizon * e.syn_.M;
+    d["episode"] = (int64_t)w[0];
+    d["base"] = (int64_t)w[1];
+    return d;
+}
+
 // Host copy of `count` replay rows starting at ring slot `base` (wrapping),
 // in ring order.
 static py::tuple replay_slice(int64_t h, int64_t base, int64_t count) {
@@ -412,13 +464,19 @@ static py::tuple replay_slice(int64_t h, int64_t base, int64_t count) {
                           grab(e.ws.rd, 1));
 }
 
-// (base, rows) of the last rollout episode, of either kind
+// (base, rows) of the last rollout episode, of any kind
 static py::tuple rollout_last(int64_t h) {
     Engine& e = get(h);
     if (e.roll_kind_ == Engine::ROLL_GOAL) {
         long long w[5];
         e.goal_rollout_words(w);
         return py::make_tuple((int64_t)w[1], (int64_t)w[2]);
+    }
+    if (e.roll_kind_ == Engine::ROLL_SYNTH) {
+        long long w[2];
+        e.synth_rollout_words(w);
+        return py::make_tuple((int64_t)w[1],
+                              (int64_t)e.syn_emits_per_ep * e.syn_.M);
     }
     if (e.roll_kind_ != Engine::ROLL_PENDULUM)
         throw std::runtime_error("no rollout allocated");
@@ -533,6 +591,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("goal_rollout_set_state", &d4pg::goal_rollout_set_state);
     mod.def("goal_rollout_info", &d4pg::goal_rollout_info);
     mod.def("goal_rollout_episode", &d4pg::goal_rollout_episode);
+    mod.def("synth_rollout_alloc", &d4pg::synth_rollout_alloc);
+    mod.def("synth_rollout_run", &d4pg::synth_rollout_run);
+    mod.def("synth_rollout_set_state", &d4pg::synth_rollout_set_state);
+    mod.def("synth_rollout_info", &d4pg::synth_rollout_info);
     mod.def("replay_slice", &d4pg::replay_slice);
     mod.def("rollout_last", &d4pg::rollout_last);
     mod.def("actor_forward", &d4pg::actor_forward);

@@ -216,6 +216,61 @@ class DistributedD4PG:
                 eps=getattr(args, "noise_eps", 0.3),
                 ou_theta=args.ou_theta, ou_sigma=args.ou_sigma,
                 ou_mu=args.ou_mu, seed=seed + 37)
+        # vectorized synthetic-spec actor, any (obs, act): M SyntheticEnv
+        # twins per actor rank (VectorSynthetic + VecNStep on the CPU); when
+        # the rank has a GPU, the device synthetic rollout instead — env,
+        # policy forward, noise and n-step fold as HIP kernels
+        # (ops/hip/engine_synth.hip), one hipGraph per episode.  The test is
+        # on the made env's instance, not its id: a gym install would
+        # resolve the same id to a real simulator.
+        self.synth_engine = False
+        base_env = getattr(self.env, "wrapped", self.env)
+        from ..envs.synthetic import SyntheticEnv
+        if (int(getattr(args, "vector_envs", 0)) > 0 and not args.her
+                and isinstance(base_env, SyntheticEnv)):
+            m = int(args.vector_envs)
+            # every rank must agree on the wire size
+            self.push_cap = m * args.max_steps
+            if not self.is_learner and not self.is_evaluator:
+                from ..envs.vector import VecNStep, VectorSynthetic
+                act_high = float(base_env.action_space.high[0])
+                self.vector = VectorSynthetic(
+                    m, self.obs_dim, self.act_dim, horizon=args.max_steps,
+                    act_high=act_high, seed=seed, noise_seed=seed + 17)
+                # one seed names one env: the twin's mixing matrices must
+                # be those of this rank's scalar env; reset states and
+                # process noise draw from a stream apart from self.rng,
+                # which supplies the exploration noise
+                if not (np.array_equal(self.vector.W,
+                                       base_env.W.astype(np.float32))
+                        and np.array_equal(self.vector.U,
+                                           base_env.U.astype(np.float32))):
+                    raise RuntimeError(
+                        "VectorSynthetic(seed) did not reproduce the mixing "
+                        "matrices of the SyntheticEnv made with the same "
+                        "seed: the vector actor would simulate another env")
+                self.vfold = VecNStep(m, self.obs_dim, self.act_dim,
+                                      args.n_steps, args.gamma)
+                if ga != 0 and torch.cuda.is_available():
+                    from ..ops import FusedEngine
+                    cap = m * max(1, args.max_steps - args.n_steps + 1)
+                    self.roll_engine = FusedEngine(
+                        obs_dim=self.obs_dim, act_dim=self.act_dim,
+                        hidden=256, n_atoms=args.n_atoms, batch=64,
+                        capacity=cap, v_min=args.v_min, v_max=args.v_max,
+                        gamma_n=args.gamma ** args.n_steps, tau=args.tau,
+                        lr_actor=1e-4, lr_critic=1e-4, seed=seed + 31)
+                    self.roll_engine.synth_rollout_alloc(
+                        m, args.n_steps, self.vector.W, self.vector.U,
+                        horizon=args.max_steps, gamma=args.gamma,
+                        act_high=act_high,
+                        proc_sigma=float(self.vector.proc_sigma),
+                        noise=getattr(args, "noise", "gaussian"),
+                        eps=float(getattr(args, "noise_eps", 0.3)),
+                        ou_theta=args.ou_theta,
+                        ou_sigma=args.ou_sigma, ou_mu=args.ou_mu,
+                        seed=seed + 37)
+                    self.synth_engine = True
         # vector-actor exploration noise honors --noise/--noise_eps/--ou_*
         # (this path used to hardcode eps=0.3).  OU
         # runs batched over [M, act]; Gaussian stays a one-liner below.
@@ -364,6 +419,15 @@ class DistributedD4PG:
                 gamma=self.args.gamma, rng=self.rng)
             self.env_meter.add(int(length.sum()))
             self._log_success(float(succ.mean()))
+            return lb
+        if self.synth_engine:
+            # device synthetic rollout: only the last episode's rows are
+            # shipped (the replay capacity may exceed one episode)
+            from ..ops import pack_net as _pack
+            self.roll_engine.load_slab("actor", _pack(self.agent.actor))
+            env_steps, _ = self.roll_engine.synth_rollout_run(1)
+            lb.add_batch(*self.roll_engine.rollout_last_rows())
+            self.env_meter.add(env_steps)
             return lb
         if self.roll_engine is not None:
             # device rollout: load the freshly broadcast policy into the
