@@ -106,6 +106,24 @@ __device__ inline float act_mask(int act, float h) {
     return 1.f;
 }
 
+// Write-through store and L1-bypassing load for data one workgroup hands to
+// another INSIDE a launch without a cache fence (the persistent kernel's quad
+// and crew hand-offs, engine_persistent.hip): global_store_dword /
+// global_load_dword ... sc1.  The store leaves no dirty line for a release
+// fence to write back; the load is served by L2, never by a line this CU's
+// L1 still holds from an earlier step.  The address_space(1) casts keep both
+// `global_`: pointer parameters of __noinline__ functions are generic, and
+// a flat_ load is not a valid hand-off load.
+typedef __attribute__((address_space(1))) float gfloat;
+__device__ __forceinline__ void st_wt(float* p, float v) {
+    __hip_atomic_store((gfloat*)p, v, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ float ld_wt(const float* p) {
+    return __hip_atomic_load((const gfloat*)p, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Layer pointer bundle for a net slab.
 struct NetPtrs { const float *w1, *b1, *w2, *b2, *w3, *b3, *w4, *b4; };
 

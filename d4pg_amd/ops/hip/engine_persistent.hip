@@ -1,13 +1,21 @@
 // Persistent whole-step megakernel k_step_persistent and its p_* phase helpers.
 // Used by whole train steps at B <= 256, the flagship regime: ONE kernel runs
-// the step (and an nsteps loop of steps) as ~27 layer-parallel phases over 96
-// co-resident workgroups separated by a software grid barrier (tree arrival +
-// write-once go-flag).  Each GEMM/dX phase tiles 4 rows x 64 cols per
-// workgroup with register-batched, double-buffered LDS staging; at B <= 64 the
-// PER write-back, the next step's sampling and its critic forward hide beside
-// the row-local quad chains (elsewhere under the dW/Adam phases).  At B=64
-// the step is latency-bound (PMC: 3% VALUBusy), so the design maximizes
-// memory-level parallelism, not FLOPs.
+// the step (and an nsteps loop of steps) as layer-parallel phases over PNWG =
+// 96 co-resident workgroups separated by a software grid barrier (tree
+// arrival + write-once go-flag): 7 grid barriers per steady-state step at
+// B <= 64, 12 on a launch's first step.  Each GEMM/dX phase tiles 4 rows x 64
+// cols per workgroup with register-batched, double-buffered LDS staging; at
+// B <= 64 the PER write-back, the next step's sampling and its critic forward
+// hide beside the row-local quad chains (elsewhere under the dW/Adam phases).
+// At B=64 the step is latency-bound (PMC: 3% VALUBusy), so the design
+// maximizes memory-level parallelism, not FLOPs.
+//
+// HAND-OFF RULE.  Inside a phase, workgroups pass data through q_bar / t_bar,
+// which carry NO cache fence: every store another workgroup reads before the
+// phase's closing p_bar is a write-through st_wt(), and every load of bytes
+// another workgroup wrote inside the current phase is an ld_wt() into
+// registers.  A new load of in-phase data must be an ld_wt() load.  Only
+// p_bar, the grid barrier, writes L2 back and invalidates L1.
 
 namespace d4pg {
 
@@ -22,10 +30,10 @@ namespace d4pg {
 // CE/policy grads -> dX/dW backward -> Adam+soft-update -> PER write-back)
 // as ONE persistent kernel: PNWG=96 workgroups x 256 threads (guaranteed
 // co-resident on 256 CUs, so a software grid barrier is deadlock-free),
-// ~28 layer-parallel phases separated by grid barriers.  Each phase tiles
-// its GEMM over the grid (16-row x 64-col tiles, x rows staged in LDS,
+// layer-parallel phases separated by grid barriers.  Each phase tiles
+// its GEMM over the grid (4-row x 64-col tiles, x rows staged in LDS,
 // weight columns read once per row-tile instead of once per row), so
-// weight traffic drops ~16x and every phase has 16-64 workgroups of
+// weight traffic drops ~4x and every phase has 16-64 workgroups of
 // parallelism.  nsteps loop inside the kernel => zero host involvement
 // between steps (the hipGraph path is only needed for the wide-batch
 // configs that use the per-layer kernels above).
@@ -58,13 +66,14 @@ namespace d4pg {
         (g).tstamp[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define PTIME(g, s, i) PTIMEW(g, s, i, 0)
 
-// The barriers' two fences are one-directional: the release before an
-// arrival writes this workgroup's stores back, the acquire after the wait
-// drops the CU's stale L1 lines.  (__threadfence() does both; two of them
-// per barrier cost the flagship step ~19 us over the 7 grid and 17 quad
-// barriers of its critical path — 4616 -> 5041 steps/s, NOTES.md.)  The
-// explicit vmcnt wait keeps the arrival, and the loads after the barrier,
-// behind the fence's own wait.
+// Only p_bar, the grid barrier, still fences, and its two fences are
+// one-directional: the release before the arrival writes this workgroup's
+// stores back, the acquire after the wait drops the CU's stale L1 lines.
+// (__threadfence() does both; two of them per barrier cost the flagship
+// step ~19 us — 4616 -> 5041 steps/s, NOTES.md.)  The explicit vmcnt wait
+// keeps the arrival, and the loads after the barrier, behind the fence's
+// own wait.  q_bar and t_bar carry no fence at all: what crosses them
+// follows the hand-off rule in the file header (st_wt / ld_wt below).
 __device__ inline void bar_release() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -72,6 +81,30 @@ __device__ inline void bar_release() {
 __device__ inline void bar_acquire() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+typedef __attribute__((address_space(1))) unsigned long long gu64;
+
+// Fence-free arrival + wait of q_bar / t_bar: every wave drains its own
+// write-through stores, the workgroup barrier collects the waves, one lane
+// adds to the group's counter and polls it with L1-bypassing loads.  The
+// wavefront-scope fence emits no instruction; it keeps the compiler from
+// hoisting loads above the poll.  Bounded spin as in p_bar.
+__device__ __forceinline__ void bar_handoff(unsigned long long* ctr,
+                                            unsigned long long want) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(ctr, 1ull);
+        long spins = 0;
+        while (__hip_atomic_load((gu64*)ctr, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT) < want) {
+            if (++spins > (1L << 26)) break;
+            __builtin_amdgcn_s_sleep(1);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
 }
 
 // software grid barrier — tree arrival + write-once go-flag.  Safe because
@@ -139,23 +172,11 @@ __device__ inline void p_bar(unsigned long long* gb,
 // proceed fully independently (~0.5-1 us vs ~3.3 us for the grid form).
 // qround carries across launches like the grid round: members read the
 // line once at kernel entry (ordered before any arrival by the first
-// grid barrier) and count from there.
+// grid barrier) and count from there.  No fence: see bar_handoff.
 __device__ inline void q_bar(unsigned long long* qc,
                              unsigned long long& qround) {
-    __syncthreads();
     qround += 4;
-    if (threadIdx.x == 0) {
-        bar_release();
-        atomicAdd(qc, 1ull);
-        volatile unsigned long long* f = qc;
-        long spins = 0;
-        while (*f < qround) {
-            if (++spins > (1L << 26)) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        bar_acquire();
-    }
-    __syncthreads();
+    bar_handoff(qc, qround);
 }
 // (A per-member slot-store variant — release stores + one-line relaxed
 // polls instead of the shared atomic counter — measured SLOWER: 3674 vs
@@ -165,28 +186,18 @@ __device__ inline void q_bar(unsigned long long* qc,
 // member count; own line at gbar[1280])
 __device__ inline void t_bar(unsigned long long* tc,
                              unsigned long long& trnd, int members) {
-    __syncthreads();
     trnd += members;
-    if (threadIdx.x == 0) {
-        bar_release();
-        atomicAdd(tc, 1ull);
-        volatile unsigned long long* f = tc;
-        long spins = 0;
-        while (*f < trnd) {
-            if (++spins > (1L << 26)) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        bar_acquire();
-    }
-    __syncthreads();
+    bar_handoff(tc, trnd);
 }
 
-// Tiled forward: 16-row x 64-col tiles; x rows staged in LDS (broadcast
-// reads), weight column read ONCE per tile (not once per row).  Thread
-// (rq = tid/64, c = tid%64) accumulates rows {r0+rq, +4, +8, +12} of column
-// c0+c — four independent FMA chains for ILP; softmax (out<=64) reduces
-// per-row across the wave.  Summation order over k is ascending, matching
-// the eager/rowblock paths bit-for-bit.
+// Tiled forward: 4-row x 64-col tiles, one row per wave; x rows staged in
+// LDS (broadcast reads), weight column read ONCE per tile (not once per
+// row).  Thread (rq = tid/64, c = tid%64) accumulates row r0+rq of column
+// c0+c; softmax (out<=64) reduces per-row across the wave.  Summation order
+// over k is ascending, matching the eager/rowblock paths bit-for-bit.
+// x1 / x2 may have been written by another workgroup inside this phase and
+// y may be read by one: ld_wt loads, st_wt stores, whoever calls (the
+// hand-off rule).  Weights and biases were published behind a p_bar.
 // (__noinline__ is load-bearing: inlining 15 copies into the persistent
 // kernel segfaults ROCm 7.2's clang in ADCE; the call overhead is noise
 // next to the ~1 us phase time.)
@@ -232,8 +243,8 @@ __device__ __noinline__ void p_fwd(float* lds, const float* x1, const float* x2,
                         int gb = r0 + rr_;
                         if (gb < B && kk < in_total)
                             v = (kk < in1)
-                                ? x1[(long)gb * in1 + kk]
-                                : x2[(long)gb * in2 + (kk - in1)];
+                                ? ld_wt(&x1[(long)gb * in1 + kk])
+                                : ld_wt(&x2[(long)gb * in2 + (kk - in1)]);
                     }
                     tmp[u] = v;
                 }
@@ -309,12 +320,12 @@ __device__ __noinline__ void p_fwd(float* lds, const float* x1, const float* x2,
             float e = (o < out) ? __expf(v - mx) : 0.f;
             float sum = e;
             for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s, 64);
-            if (r < B && o < out) y[(long)r * out + o] = e / sum;
+            if (r < B && o < out) st_wt(&y[(long)r * out + o], e / sum);
         } else if (r < B && o < out) {
             float v = acc + bias[o];
             if (act_kind == ACT_RELU) v = fmaxf(v, 0.f);
             else if (act_kind == ACT_TANH) v = tanhf(v);
-            y[(long)r * out + o] = v;
+            st_wt(&y[(long)r * out + o], v);
         }
         __syncthreads();
     }
@@ -323,6 +334,7 @@ __device__ __noinline__ void p_fwd(float* lds, const float* x1, const float* x2,
 // Tiled backward-dX: dx[b][i-in_lo] = (sum_o dz[b][o] wt[i][o]) * mask.
 // dz rows staged in LDS; mask/dx arrays are [B][span] (span = in_hi-in_lo):
 // full-range h arrays and the concat action slice both fit this form.
+// dz and hprev are ld_wt loads and dx an st_wt store (the hand-off rule).
 __device__ inline void p_bwd_dx(float* lds, const float* dz, const float* wt,
                                 int in_lo, int in_hi, int out, int B,
                                 const float* hprev, int prev_act, float* dx,
@@ -363,7 +375,7 @@ __device__ inline void p_bwd_dx(float* lds, const float* dz, const float* wt,
                         int rr_ = e / out_pad, oo = e % out_pad;
                         int gb = r0 + rr_;
                         if (gb < B && oo < out)
-                            v = dz[(long)gb * out + oo];
+                            v = ld_wt(&dz[(long)gb * out + oo]);
                     }
                     tmp[u] = v;
                 }
@@ -427,8 +439,8 @@ __device__ inline void p_bwd_dx(float* lds, const float* dz, const float* wt,
         }
         if (r < B && i < in_hi) {
             long rel = (long)r * span + (i - in_lo);
-            float m_ = hprev ? act_mask(prev_act, hprev[rel]) : 1.f;
-            dx[rel] = acc * m_;
+            float m_ = hprev ? act_mask(prev_act, ld_wt(&hprev[rel])) : 1.f;
+            st_wt(&dx[rel], acc * m_);
         }
         __syncthreads();
     }
@@ -596,7 +608,10 @@ __device__ inline void p_project_ce(const StepArgs& g, float* lds,
     if (row >= g.B) return;
     int K = g.K;
     float* mrow = lds + wid * 64;
-    float p = (lane < K) ? g.p_t[(long)row * K + lane] : 0.f;
+    // p_t: this workgroup's own st_wt store of a moment ago (K <= 64 is one
+    // column tile, member 0's); ld_wt so that no older L1 line can serve it.
+    // q, br, bd, bw and the stores below cross a p_bar: plain.
+    float p = (lane < K) ? ld_wt(&g.p_t[(long)row * K + lane]) : 0.f;
     c51_project_row(mrow, p, g.br[row], g.bd[row], g.v_min, g.v_max,
                     g.gamma_n, K, lane);
     float qv = 0.f, mv = 0.f;
@@ -619,7 +634,8 @@ __device__ inline void p_project_ce(const StepArgs& g, float* lds,
 
 // narrow backward-dX (span <= 8, e.g. the concat action slice): one wave
 // per batch row, lane-parallel dot over `out` with a shfl reduce, tanh
-// mask applied from ymask.
+// mask applied from ymask.  dz and ymask are handed off in-phase (ld_wt),
+// dx is read by the next layer's quad (st_wt).
 __device__ inline void p_bwd_dx_narrow(const StepArgs& g, const float* dz,
                                        const float* wt, int in_lo,
                                        int in_hi, int out,
@@ -634,11 +650,11 @@ __device__ inline void p_bwd_dx_narrow(const StepArgs& g, const float* dz,
         const float* wrow = wt + (long)(in_lo + j) * out;
         float acc = 0.f;
         for (int o = lane; o < out; o += 64)
-            acc += dz[(long)row * out + o] * wrow[o];
+            acc += ld_wt(&dz[(long)row * out + o]) * wrow[o];
         for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, 64);
         if (lane == 0) {
-            float y = ymask[(long)row * span + j];
-            dx[(long)row * span + j] = acc * (1.f - y * y);
+            float y = ld_wt(&ymask[(long)row * span + j]);
+            st_wt(&dx[(long)row * span + j], acc * (1.f - y * y));
         }
     }
 }
@@ -650,11 +666,15 @@ __device__ inline void p_policy_grad(const StepArgs& g,
     int lane = threadIdx.x & 63;
     if (row >= g.B) return;
     int K = g.K;
-    float qv = (lane < K) ? g.pq[(long)row * K + lane] : 0.f;
+    // pq: K <= 64 (step_path's gate) makes pc.L4 ONE column tile, member
+    // 0's, and member 0 alone calls this: the rows read here are this
+    // workgroup's own st_wt stores, no other workgroup's.  ld_wt all the
+    // same, so that no older L1 line can serve them.
+    float qv = (lane < K) ? ld_wt(&g.pq[(long)row * K + lane]) : 0.f;
     float e;
     float dz = policy_grad_row(qv, c51_atom(g.v_min, g.v_max, K, lane), g.B,
                                e);
-    if (lane < K) g.pd3[(long)row * K + lane] = dz;
+    if (lane < K) st_wt(&g.pd3[(long)row * K + lane], dz);
     if (lane == 0) atomicAdd(&g.cnt->loss_actor, -e / (float)g.B);
 }
 

@@ -165,7 +165,10 @@ __device__ __forceinline__ float per_is_weight(double p, double p_min,
 // Gather tail of both sample helpers: lane 0 holds the drawn slot and has
 // written bidx / bw / br / bd; all lanes cooperatively gather the transition
 // row into the batch SoA, states into bs_out.  NT keeps the gathered replay
-// rows (random, never re-read) out of L2.
+// rows (random, never re-read) out of L2.  NT is the persistent kernel's
+// form: its tail crew reads bs / bs2 / ba across a fence-free crew barrier,
+// so there the three gather stores are write-through (st_wt).  bidx / bw /
+// br / bd are read only behind a grid barrier and stay plain.
 template <bool NT>
 __device__ __forceinline__ void sample_gather_row(const StepArgs& g,
                                                   float* bs_out, int probe,
@@ -173,13 +176,16 @@ __device__ __forceinline__ void sample_gather_row(const StepArgs& g,
     auto ld = [](const float* p) {
         return NT ? __builtin_nontemporal_load(p) : *p;
     };
+    auto st = [](float* p, float v) {
+        if (NT) st_wt(p, v); else *p = v;
+    };
     idx = __shfl(idx, 0, 64);
     for (int k = lane; k < g.O; k += 64) {
-        bs_out[(long)probe * g.O + k] = ld(&g.rs[idx * g.O + k]);
-        g.bs2[(long)probe * g.O + k] = ld(&g.rs2[idx * g.O + k]);
+        st(&bs_out[(long)probe * g.O + k], ld(&g.rs[idx * g.O + k]));
+        st(&g.bs2[(long)probe * g.O + k], ld(&g.rs2[idx * g.O + k]));
     }
     for (int k = lane; k < g.A; k += 64)
-        g.ba[(long)probe * g.A + k] = ld(&g.ra[idx * g.A + k]);
+        st(&g.ba[(long)probe * g.A + k], ld(&g.ra[idx * g.A + k]));
 }
 
 // PER sample + gather of one probe by one wave: lane 0 walks the sum tree

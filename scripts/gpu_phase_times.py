@@ -39,6 +39,15 @@ INNER = [
     ("policy: tail crew end", 52, 14),
 ]
 
+# quad 0's walk through the policy megachain: each slot is one layer tile
+# plus the quad barrier that hands its output on (the last has none)
+POLICY_SLOTS = [
+    ("pc.L1", 40, 41), ("pc.L2", 41, 42), ("pc.L3", 42, 43),
+    ("pc.L4 + pgrad", 43, 44), ("dX c.w4", 44, 45), ("dX c.w3", 45, 46),
+    ("dX narrow (a)", 46, 47), ("dX a.w4", 47, 48), ("dX a.w3", 48, 49),
+    ("dX a.w2, no barrier", 49, 51),
+]
+
 first = "--first" in sys.argv[1:]
 eng = make_engine()
 eng.step(50)          # warm; stamps overwritten each launch
@@ -55,3 +64,5 @@ print(f"{'TOTAL':18s} {total:8.2f} us (stamped step "
 for name, slot, base in INNER:
     if ts[slot] > ts[base]:               # not stamped on this schedule
         print(f"{name:24s} +{(ts[slot] - ts[base]) / 100.0:7.2f} us")
+for name, lo, hi in POLICY_SLOTS:
+    print(f"policy slot {name:20s} {(ts[hi] - ts[lo]) / 100.0:7.2f} us")
