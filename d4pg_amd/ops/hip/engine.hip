@@ -27,6 +27,7 @@
 #include "engine_replay.hip"
 #include "engine_layer.hip"
 #include "engine_rowblock.hip"
+#include "engine_rollcore.hip"
 #include "engine_rollout.hip"
 #include "engine_goal.hip"
 #include "engine_synth.hip"
@@ -828,21 +829,42 @@ public:
         return h;
     }
 
-    // ---------------- GPU-resident rollout (device env + K11 + K15) -----
-    // See the kernel-section comment above k_roll_begin.  State lives in a
-    // separate pool so rollout capacity is independent of the learner
-    // batch; the actor weights and the replay are SHARED with the learner
-    // (same p_actor slab, same rs/../sum_tree), which is the point: the
-    // whole actor->replay->learner loop stays in HBM.
+    // ---------------- GPU-resident rollouts (device env + K11 + K15) -----
+    // Three producers over one scaffold: Pendulum (engine_rollout.hip),
+    // GoalReach with HER (engine_goal.hip) and the synthetic-spec envs of
+    // any (obs, act) (engine_synth.hip).  They share the device core
+    // (engine_rollcore.hip) and, below, the pool builder, fill_core, the
+    // policy chain, the episode graph and its runner; one producer is
+    // allocated at a time (roll_kind_).  State lives in a separate pool so
+    // rollout capacity is independent of the learner batch; the actor
+    // weights and the replay are SHARED with the learner (same p_actor
+    // slab, same rs/../sum_tree), which is the point: the whole
+    // actor->replay->learner loop stays in HBM.
     RollArgs roll_{};
+    GoalRollArgs goal_{};
+    SynRollArgs syn_{};
+    // The synth env's mixing matrices live in the pool as one layer slab
+    // ([W; U] is already [in][out], plus a zero bias), so the mixing GEMM
+    // is a plain forward job with a concat input.
+    float* syn_dyn_ = nullptr;
+    LayerDesc syn_dyn_desc_{};
     void* roll_pool_ = nullptr;
     float *r_h1 = nullptr, *r_h2 = nullptr, *r_h3 = nullptr;
     hipGraph_t roll_graph = nullptr;
     hipGraphExec_t roll_graph_exec = nullptr;
-    int roll_emits_per_ep = 0;
     // which producer owns roll_pool_ and the episode graph
     enum { ROLL_NONE = 0, ROLL_PENDULUM = 1, ROLL_GOAL = 2, ROLL_SYNTH = 3 };
     int roll_kind_ = ROLL_NONE;
+
+    RollCore& roll_core() {
+        if (roll_kind_ == ROLL_GOAL) return goal_;
+        if (roll_kind_ == ROLL_SYNTH) return syn_;
+        return roll_;
+    }
+
+    void roll_require(int kind, const char* otherwise) {
+        if (roll_kind_ != kind) throw std::runtime_error(otherwise);
+    }
 
     void rollout_free() {
         if (roll_graph_exec) { hipGraphExecDestroy(roll_graph_exec);
@@ -852,52 +874,55 @@ public:
         roll_kind_ = ROLL_NONE;
     }
 
-    void rollout_alloc(int M, int nsteps, int horizon, float gamma,
-                       int noise_kind, float eps, float ou_theta,
-                       float ou_sigma, float ou_mu, uint64_t seed) {
-        if (cfg.obs != 3 || cfg.act != 1)
-            throw std::runtime_error(
-                "device rollout models Pendulum dynamics (obs=3, act=1)");
-        if (horizon < nsteps)
+    // What every producer's args share: geometry, noise, seed and the
+    // replay the rows go to, with the refusals that hold for all of them.
+    void fill_core(RollCore& c, int M, int nsteps, int horizon, float gamma,
+                   int noise_kind, float eps, float ou_theta, float ou_sigma,
+                   float ou_mu, uint64_t seed) {
+        if (M < 1)
+            throw std::runtime_error("rollout: n_envs < 1");
+        if (nsteps < 1 || horizon < nsteps)
             throw std::runtime_error("rollout horizon < n_steps");
+        c.M = M; c.n = nsteps; c.horizon = horizon;
+        c.gamma = gamma; c.eps = eps; c.ou_theta = ou_theta;
+        c.ou_sigma = ou_sigma; c.ou_mu = ou_mu; c.ou_dt = 1e-2f;
+        c.noise_kind = noise_kind; c.seed = seed;
+        c.per_alpha = cfg.per_alpha;
+        c.rs = ws.rs; c.ra = ws.ra; c.rr = ws.rr; c.rs2 = ws.rs2; c.rd = ws.rd;
+        c.sum_tree = ws.sum_tree; c.min_tree = ws.min_tree;
+        c.tree_cap = ws.tree_cap; c.capacity = cfg.capacity;
+        c.cnt = ws.cnt;
+    }
+
+    // Frees the previous producer's pool and builds this one's.
+    // carve(sub) names each of the producer's own buffers once, as
+    // sub(pointer, nelem) in 4-byte words; the core's device words and the
+    // policy chain's hidden buffers are carved here.  carve runs twice: to
+    // size the pool, then to point the buffers into the cleared allocation.
+    template <class Carve>
+    void roll_pool_build(RollCore& c, Carve carve) {
         rollout_free();
-        RollArgs a{};
-        a.M = M; a.O = 3; a.A = 1; a.n = nsteps; a.horizon = horizon;
-        a.gamma = gamma; a.eps = eps; a.ou_theta = ou_theta;
-        a.ou_sigma = ou_sigma; a.ou_mu = ou_mu; a.ou_dt = 1e-2f;
-        a.noise_kind = noise_kind; a.seed = seed;
-        a.per_alpha = cfg.per_alpha;
-        const int H = cfg.hidden;
+        char* base = nullptr;
         long off = 0;
-        auto sub = [&](long nelem) {
-            long o = off;
+        auto sub = [&](auto*& p, long nelem) {
+            if (base) p = reinterpret_cast<decltype(+p)>(base + off);
             off += (nelem * 4 + 255) & ~255L;
-            return o;
         };
-        long o_th = sub(M), o_td = sub(M), o_obs = sub((long)M * 3),
-             o_act = sub(M), o_ou = sub(M),
-             o_sr = sub((long)nsteps * M * 3), o_ar = sub((long)nsteps * M),
-             o_rr = sub((long)nsteps * M), o_ep = sub(4),
-             o_h1 = sub((long)M * H), o_h2 = sub((long)M * H),
-             o_h3 = sub((long)M * H);
+        auto carve_all = [&] {
+            off = 0;
+            carve(sub);
+            sub(c.ep_state, 16);                // 8 words of 8 bytes
+            const long MH = (long)c.M * cfg.hidden;
+            sub(r_h1, MH); sub(r_h2, MH); sub(r_h3, MH);
+        };
+        carve_all();
         HIP_CHECK(hipMalloc(&roll_pool_, off));
         HIP_CHECK(hipMemset(roll_pool_, 0, off));
-        char* base = (char*)roll_pool_;
-        a.th = (float*)(base + o_th); a.thdot = (float*)(base + o_td);
-        a.obs = (float*)(base + o_obs); a.act = (float*)(base + o_act);
-        a.ou_x = (float*)(base + o_ou);
-        a.s_ring = (float*)(base + o_sr); a.a_ring = (float*)(base + o_ar);
-        a.r_ring = (float*)(base + o_rr);
-        a.ep_state = (long long*)(base + o_ep);
-        r_h1 = (float*)(base + o_h1); r_h2 = (float*)(base + o_h2);
-        r_h3 = (float*)(base + o_h3);
-        a.rs = ws.rs; a.ra = ws.ra; a.rr = ws.rr; a.rs2 = ws.rs2; a.rd = ws.rd;
-        a.sum_tree = ws.sum_tree; a.min_tree = ws.min_tree;
-        a.tree_cap = ws.tree_cap; a.capacity = cfg.capacity;
-        a.cnt = ws.cnt;
-        roll_ = a;
-        roll_emits_per_ep = horizon - nsteps + 1;
-        roll_kind_ = ROLL_PENDULUM;
+        base = (char*)roll_pool_;
+        carve_all();
+        // the clear went to the null stream; the episode kernels run on the
+        // engine's non-blocking stream
+        HIP_CHECK(hipDeviceSynchronize());
     }
 
     // the policy forward obs [M][obs] -> act [M][act] between two ticks
@@ -916,10 +941,74 @@ public:
         run(r_h3, anet.l[3], act, ACT_TANH);
     }
 
-    void rollout_enqueue_episode(bool reset) {
+    // one whole episode of the allocated producer, on the engine's stream
+    void enqueue_episode(bool reset) {
+        hipLaunchKernelGGL(k_roll_begin, dim3(1), dim3(64), 0, stream,
+                           roll_core());
+        if (roll_kind_ == ROLL_GOAL) goal_enqueue_ticks(reset);
+        else if (roll_kind_ == ROLL_SYNTH) synth_enqueue_ticks(reset);
+        else pendulum_enqueue_ticks(reset);
+        // internal tree nodes: one bandwidth-bound full sweep per episode
+        // (vs horizon x per-path repair) — leaves were set at emit; a no-op
+        // on uniform replay
+        launch_tree_rebuild(1024);
+    }
+
+    // `episodes` whole episodes and the synchronise after them; with
+    // use_graph and reset, one captured graph launched once per episode
+    void run_episodes(int episodes, bool reset, bool use_graph) {
+        if (use_graph && reset) {
+            if (!roll_graph_exec) {
+                HIP_CHECK(hipStreamBeginCapture(
+                    stream, hipStreamCaptureModeThreadLocal));
+                enqueue_episode(true);
+                HIP_CHECK(hipStreamEndCapture(stream, &roll_graph));
+                HIP_CHECK(hipGraphInstantiate(&roll_graph_exec, roll_graph,
+                                              nullptr, nullptr, 0));
+            }
+            for (int e = 0; e < episodes; ++e)
+                HIP_CHECK(hipGraphLaunch(roll_graph_exec, stream));
+        } else {
+            for (int e = 0; e < episodes; ++e)
+                enqueue_episode(reset);
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+
+    // the per-episode device words of the last episode: [0] philox epoch,
+    // [1] replay base, [2] rows emitted, and the goal rollout's [3]
+    // successes, [4] env steps
+    void rollout_words(long long (&w)[5]) {
+        if (roll_kind_ == ROLL_NONE)
+            throw std::runtime_error("no rollout allocated");
+        HIP_CHECK(hipMemcpy(w, roll_core().ep_state, sizeof(w),
+                            hipMemcpyDeviceToHost));
+    }
+
+    // ---------------- Pendulum rollout (engine_rollout.hip) --------------
+    void rollout_alloc(int M, int nsteps, int horizon, float gamma,
+                       int noise_kind, float eps, float ou_theta,
+                       float ou_sigma, float ou_mu, uint64_t seed) {
+        if (cfg.obs != 3 || cfg.act != 1)
+            throw std::runtime_error(
+                "device rollout models Pendulum dynamics (obs=3, act=1)");
+        RollArgs a{};
+        fill_core(a, M, nsteps, horizon, gamma, noise_kind, eps, ou_theta,
+                  ou_sigma, ou_mu, seed);
+        a.O = 3; a.A = 1;
+        const long nM = (long)nsteps * M;
+        roll_pool_build(a, [&](auto& sub) {
+            sub(a.th, M); sub(a.thdot, M); sub(a.obs, 3L * M);
+            sub(a.act, M); sub(a.ou_x, M);
+            sub(a.s_ring, 3 * nM); sub(a.a_ring, nM); sub(a.r_ring, nM);
+        });
+        roll_ = a;
+        roll_kind_ = ROLL_PENDULUM;
+    }
+
+    void pendulum_enqueue_ticks(bool reset) {
         RollArgs& a = roll_;
         int wgs = ceil_div(a.M, 256);
-        hipLaunchKernelGGL(k_roll_begin, dim3(1), dim3(64), 0, stream, a);
         if (reset)
             hipLaunchKernelGGL(k_roll_reset, dim3(wgs), dim3(256), 0,
                                stream, a);
@@ -932,32 +1021,13 @@ public:
                                a, t, t % a.n, ek, done);
             if (ek >= 0) ++emit_k;
         }
-        hipLaunchKernelGGL(k_roll_end, dim3(1), dim3(64), 0, stream, a,
-                           (long)emit_k * a.M);
-        // internal tree nodes: one bandwidth-bound full sweep per episode
-        // (vs horizon x per-path repair) — leaves were set at emit
-        launch_tree_rebuild(1024);
+        hipLaunchKernelGGL(k_roll_end, dim3(1), dim3(64), 0, stream,
+                           (RollCore&)a, (long)emit_k * a.M);
     }
 
     void rollout_run(int episodes, bool reset, bool use_graph) {
-        if (roll_kind_ != ROLL_PENDULUM)
-            throw std::runtime_error("rollout_alloc first");
-        if (use_graph && reset) {
-            if (!roll_graph_exec) {
-                HIP_CHECK(hipStreamBeginCapture(
-                    stream, hipStreamCaptureModeThreadLocal));
-                rollout_enqueue_episode(true);
-                HIP_CHECK(hipStreamEndCapture(stream, &roll_graph));
-                HIP_CHECK(hipGraphInstantiate(&roll_graph_exec, roll_graph,
-                                              nullptr, nullptr, 0));
-            }
-            for (int e = 0; e < episodes; ++e)
-                HIP_CHECK(hipGraphLaunch(roll_graph_exec, stream));
-        } else {
-            for (int e = 0; e < episodes; ++e)
-                rollout_enqueue_episode(reset);
-        }
-        HIP_CHECK(hipStreamSynchronize(stream));
+        roll_require(ROLL_PENDULUM, "rollout_alloc first");
+        run_episodes(episodes, reset, use_graph);
     }
 
     // test hook: inject exact env state (parity vs the numpy oracle)
@@ -980,12 +1050,7 @@ public:
                             hipMemcpyHostToDevice));
     }
 
-    // ---------------- GPU-resident goal rollout + HER (engine_goal.hip) ----
-    // Shares the pool pointer, the hidden buffers, the episode graph and
-    // rollout_free() with the Pendulum rollout; one of the two is allocated
-    // at a time (roll_kind_).
-    GoalRollArgs goal_{};
-
+    // ---------------- goal rollout + HER (engine_goal.hip) ---------------
     // rows one episode can emit at most: every env runs to the step limit
     // and every step gets a hindsight row
     static long goal_episode_max(long M, long nsteps, long horizon) {
@@ -999,10 +1064,11 @@ public:
         if (cfg.act < 1 || cfg.obs != 2 * cfg.act)
             throw std::runtime_error(
                 "device goal rollout needs obs = [pos, goal] (obs == 2*act)");
-        if (M < 1 || M > 65536)
+        GoalRollArgs a{};
+        fill_core(a, M, nsteps, horizon, gamma, noise_kind, eps, ou_theta,
+                  ou_sigma, ou_mu, seed);
+        if (M > 65536)
             throw std::runtime_error("goal rollout: n_envs not in [1, 65536]");
-        if (nsteps < 1 || horizon < nsteps)
-            throw std::runtime_error("goal rollout horizon < n_steps");
         if (horizon >= (1 << 20))
             throw std::runtime_error("goal rollout horizon >= 2^20");
         if (cfg.capacity < goal_episode_max(M, nsteps, horizon))
@@ -1010,58 +1076,23 @@ public:
                 "goal rollout: replay capacity below one episode's maximum "
                 "M*(horizon-n+1) + M*horizon rows (two rows of one episode "
                 "would share a slot)");
-        rollout_free();
-        GoalRollArgs a{};
-        const int D = cfg.act, H = cfg.hidden;
-        a.M = M; a.D = D; a.n = nsteps; a.horizon = horizon;
-        a.gamma = gamma; a.eps = eps; a.ou_theta = ou_theta;
-        a.ou_sigma = ou_sigma; a.ou_mu = ou_mu; a.ou_dt = 1e-2f;
+        a.D = cfg.act;
         a.speed = speed; a.tol = tol; a.her_ratio = her_ratio;
-        a.noise_kind = noise_kind; a.seed = seed;
-        a.per_alpha = cfg.per_alpha;
-        long off = 0;
-        auto sub = [&](long nelem) {            // nelem 4-byte words
-            long o = off;
-            off += (nelem * 4 + 255) & ~255L;
-            return o;
-        };
-        const long MD = (long)M * D;
-        long o_pos = sub(MD), o_goal = sub(MD), o_obs = sub(2 * MD),
-             o_act = sub(MD), o_ou = sub(MD), o_alive = sub(M),
-             o_len = sub(M), o_succ = sub(M),
-             o_epp = sub((long)(horizon + 1) * MD),
-             o_epa = sub((long)horizon * MD), o_cnt = sub(M),
-             o_off = sub(2L * M), o_ep = sub(16),
-             o_h1 = sub((long)M * H), o_h2 = sub((long)M * H),
-             o_h3 = sub((long)M * H);
-        HIP_CHECK(hipMalloc(&roll_pool_, off));
-        HIP_CHECK(hipMemset(roll_pool_, 0, off));
-        // the episode kernels run on the engine's non-blocking stream
-        HIP_CHECK(hipDeviceSynchronize());
-        char* base = (char*)roll_pool_;
-        a.pos =(float*)(base + o_pos); a.goal = (float*)(base + o_goal);
-        a.obs = (float*)(base + o_obs); a.act = (float*)(base + o_act);
-        a.ou_x = (float*)(base + o_ou);
-        a.alive = (int*)(base + o_alive); a.len = (int*)(base + o_len);
-        a.succ = (int*)(base + o_succ);
-        a.ep_pos = (float*)(base + o_epp); a.ep_act = (float*)(base + o_epa);
-        a.count = (int*)(base + o_cnt);
-        a.offset = (long long*)(base + o_off);
-        a.ep_state = (long long*)(base + o_ep);
-        r_h1 = (float*)(base + o_h1); r_h2 = (float*)(base + o_h2);
-        r_h3 = (float*)(base + o_h3);
-        a.rs = ws.rs; a.ra = ws.ra; a.rr = ws.rr; a.rs2 = ws.rs2; a.rd = ws.rd;
-        a.sum_tree = ws.sum_tree; a.min_tree = ws.min_tree;
-        a.tree_cap = ws.tree_cap; a.capacity = cfg.capacity;
-        a.cnt = ws.cnt;
+        const long MD = (long)M * a.D;
+        roll_pool_build(a, [&](auto& sub) {
+            sub(a.pos, MD); sub(a.goal, MD); sub(a.obs, 2 * MD);
+            sub(a.act, MD); sub(a.ou_x, MD);
+            sub(a.alive, M); sub(a.len, M); sub(a.succ, M);
+            sub(a.ep_pos, (horizon + 1) * MD); sub(a.ep_act, horizon * MD);
+            sub(a.count, M); sub(a.offset, 2L * M);
+        });
         goal_ = a;
         roll_kind_ = ROLL_GOAL;
     }
 
-    void goal_enqueue_episode(bool reset) {
+    void goal_enqueue_ticks(bool reset) {
         GoalRollArgs& a = goal_;
         int wgs = ceil_div(a.M, 256);
-        hipLaunchKernelGGL(k_goal_begin, dim3(1), dim3(64), 0, stream, a);
         if (reset)
             hipLaunchKernelGGL(k_goal_reset, dim3(wgs), dim3(256), 0,
                                stream, a);
@@ -1078,7 +1109,6 @@ public:
         hipLaunchKernelGGL(k_goal_emit, dim3(ewgs > 2048 ? 2048 : ewgs),
                            dim3(256), 0, stream, a);
         hipLaunchKernelGGL(k_goal_end, dim3(1), dim3(64), 0, stream, a);
-        launch_tree_rebuild(1024);
     }
 
     // Totals over the episodes of one goal_rollout_run call, read from the
@@ -1086,38 +1116,13 @@ public:
     struct GoalTotals { long long rows, successes, env_steps; };
 
     GoalTotals goal_rollout_run(int episodes, bool reset, bool use_graph) {
-        if (roll_kind_ != ROLL_GOAL)
-            throw std::runtime_error("goal_rollout_alloc first");
+        roll_require(ROLL_GOAL, "goal_rollout_alloc first");
         HIP_CHECK(hipMemsetAsync(goal_.ep_state + 5, 0, 3 * 8, stream));
-        if (use_graph && reset) {
-            if (!roll_graph_exec) {
-                HIP_CHECK(hipStreamBeginCapture(
-                    stream, hipStreamCaptureModeThreadLocal));
-                goal_enqueue_episode(true);
-                HIP_CHECK(hipStreamEndCapture(stream, &roll_graph));
-                HIP_CHECK(hipGraphInstantiate(&roll_graph_exec, roll_graph,
-                                              nullptr, nullptr, 0));
-            }
-            for (int e = 0; e < episodes; ++e)
-                HIP_CHECK(hipGraphLaunch(roll_graph_exec, stream));
-        } else {
-            for (int e = 0; e < episodes; ++e)
-                goal_enqueue_episode(reset);
-        }
+        run_episodes(episodes, reset, use_graph);
         long long w[3];
-        HIP_CHECK(hipMemcpyAsync(w, goal_.ep_state + 5, sizeof(w),
-                                 hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        return {w[0], w[1], w[2]};
-    }
-
-    // the per-episode device words of the last episode: [0] philox epoch,
-    // [1] replay base, [2] rows emitted, [3] successes, [4] env steps
-    void goal_rollout_words(long long (&w)[5]) {
-        if (roll_kind_ != ROLL_GOAL)
-            throw std::runtime_error("goal_rollout_alloc first");
-        HIP_CHECK(hipMemcpy(w, goal_.ep_state, sizeof(w),
+        HIP_CHECK(hipMemcpy(w, goal_.ep_state + 5, sizeof(w),
                             hipMemcpyDeviceToHost));
+        return {w[0], w[1], w[2]};
     }
 
     // test hook: inject exact env state, leaving everything else as
@@ -1151,31 +1156,19 @@ public:
                             hipMemcpyHostToDevice));
     }
 
-    // ---------------- GPU-resident synthetic-spec rollout (engine_synth.hip)
-    // Any (obs, act).  Shares the pool pointer, the hidden buffers, the
-    // policy chain, the episode graph and rollout_free() with the other two
-    // rollouts; one is allocated at a time (roll_kind_).  The env's mixing
-    // matrices live in the pool as one layer slab ([W; U] is already
-    // [in][out], plus a zero bias), so the mixing GEMM is a plain forward
-    // job with a concat input.
-    SynRollArgs syn_{};
-    float* syn_dyn_ = nullptr;
-    LayerDesc syn_dyn_desc_{};
-    int syn_emits_per_ep = 0;
-
+    // ---------------- synthetic-spec rollout (engine_synth.hip) ----------
     void synth_rollout_alloc(int M, int nsteps, int horizon, float gamma,
                              float act_high, float proc_sigma,
                              int noise_kind, float eps, float ou_theta,
                              float ou_sigma, float ou_mu, uint64_t seed,
                              const float* W, const float* U) {
-        const int O = cfg.obs, A = cfg.act, H = cfg.hidden;
+        const int O = cfg.obs, A = cfg.act;
         if (O + A > FWD_XMAX)
             throw std::runtime_error(
                 "synth rollout: obs + act exceeds FWD_XMAX LDS tile");
-        if (M < 1)
-            throw std::runtime_error("synth rollout: n_envs < 1");
-        if (nsteps < 1 || horizon < nsteps)
-            throw std::runtime_error("synth rollout horizon < n_steps");
+        SynRollArgs a{};
+        fill_core(a, M, nsteps, horizon, gamma, noise_kind, eps, ou_theta,
+                  ou_sigma, ou_mu, seed);
         if (horizon >= (1 << 20) - 2)
             throw std::runtime_error("synth rollout horizon >= 2^20 - 2");
         if (cfg.capacity < (long)M * (horizon - nsteps + 1))
@@ -1183,58 +1176,29 @@ public:
                 "synth rollout: replay capacity below one episode's "
                 "M*(horizon-n+1) rows (two rows of one episode would share "
                 "a slot)");
-        rollout_free();
-        SynRollArgs a{};
-        a.M = M; a.O = O; a.A = A; a.n = nsteps; a.horizon = horizon;
-        a.gamma = gamma; a.eps = eps; a.ou_theta = ou_theta;
-        a.ou_sigma = ou_sigma; a.ou_mu = ou_mu; a.ou_dt = 1e-2f;
+        a.O = O; a.A = A;
         a.act_high = act_high; a.proc_sigma = proc_sigma;
-        a.noise_kind = noise_kind; a.seed = seed;
-        a.per_alpha = cfg.per_alpha;
-        long off = 0;
-        auto sub = [&](long nelem) {            // nelem 4-byte words
-            long o = off;
-            off += (nelem * 4 + 255) & ~255L;
-            return o;
-        };
         const long MO = (long)M * O, MA = (long)M * A;
         const long n_dyn = (long)(O + A) * O;
-        long o_obs = sub(MO), o_act = sub(MA), o_env = sub(MA), o_z = sub(MO),
-             o_ou = sub(MA), o_sr = sub(nsteps * MO), o_ar = sub(nsteps * MA),
-             o_rr = sub((long)nsteps * M), o_ep = sub(4),
-             o_dyn = sub(n_dyn + O),
-             o_h1 = sub((long)M * H), o_h2 = sub((long)M * H),
-             o_h3 = sub((long)M * H);
-        HIP_CHECK(hipMalloc(&roll_pool_, off));
-        HIP_CHECK(hipMemset(roll_pool_, 0, off));
-        char* base = (char*)roll_pool_;
-        a.obs = (float*)(base + o_obs); a.act = (float*)(base + o_act);
-        a.act_env = (float*)(base + o_env); a.z = (float*)(base + o_z);
-        a.ou_x = (float*)(base + o_ou);
-        a.s_ring = (float*)(base + o_sr); a.a_ring = (float*)(base + o_ar);
-        a.r_ring = (float*)(base + o_rr);
-        a.ep_state = (long long*)(base + o_ep);
-        syn_dyn_ = (float*)(base + o_dyn);
-        r_h1 = (float*)(base + o_h1); r_h2 = (float*)(base + o_h2);
-        r_h3 = (float*)(base + o_h3);
-        // [W; U] then the zero bias the memset left
-        HIP_CHECK(hipMemcpy(syn_dyn_, W, (long)O * O * 4,
+        float* dyn = nullptr;
+        roll_pool_build(a, [&](auto& sub) {
+            sub(a.obs, MO); sub(a.act, MA); sub(a.act_env, MA); sub(a.z, MO);
+            sub(a.ou_x, MA);
+            sub(a.s_ring, nsteps * MO); sub(a.a_ring, nsteps * MA);
+            sub(a.r_ring, (long)nsteps * M);
+            sub(dyn, n_dyn + O);
+        });
+        // [W; U] then the zero bias the clear left
+        HIP_CHECK(hipMemcpy(dyn, W, (long)O * O * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dyn + (long)O * O, U, (long)A * O * 4,
                             hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(syn_dyn_ + (long)O * O, U, (long)A * O * 4,
-                            hipMemcpyHostToDevice));
-        // the episode kernels run on the engine's non-blocking stream
-        HIP_CHECK(hipDeviceSynchronize());
+        syn_dyn_ = dyn;
         syn_dyn_desc_ = LayerDesc{O, A, O, 0, n_dyn};
-        a.rs = ws.rs; a.ra = ws.ra; a.rr = ws.rr; a.rs2 = ws.rs2; a.rd = ws.rd;
-        a.sum_tree = ws.sum_tree; a.min_tree = ws.min_tree;
-        a.tree_cap = ws.tree_cap; a.capacity = cfg.capacity;
-        a.cnt = ws.cnt;
         syn_ = a;
-        syn_emits_per_ep = horizon - nsteps + 1;
         roll_kind_ = ROLL_SYNTH;
     }
 
-    void synth_enqueue_episode(bool reset) {
+    void synth_enqueue_ticks(bool reset) {
         SynRollArgs& a = syn_;
         const long elems = (long)a.M * (a.O > a.A ? a.O : a.A);
         int wgs = ceil_div(elems, 256);
@@ -1242,7 +1206,6 @@ public:
         // one wave per env, four to a workgroup
         int twgs = ceil_div(a.M, 4);
         if (twgs > 2048) twgs = 2048;
-        hipLaunchKernelGGL(k_syn_begin, dim3(1), dim3(64), 0, stream, a);
         if (reset)
             hipLaunchKernelGGL(k_syn_reset, dim3(wgs), dim3(256), 0, stream,
                                a);
@@ -1262,38 +1225,13 @@ public:
                                a, t, slot, ek, done);
             if (ek >= 0) ++emit_k;
         }
-        hipLaunchKernelGGL(k_syn_end, dim3(1), dim3(64), 0, stream, a,
-                           (long)emit_k * a.M);
-        launch_tree_rebuild(1024);              // no-op on uniform replay
+        hipLaunchKernelGGL(k_roll_end, dim3(1), dim3(64), 0, stream,
+                           (RollCore&)a, (long)emit_k * a.M);
     }
 
     void synth_rollout_run(int episodes, bool reset, bool use_graph) {
-        if (roll_kind_ != ROLL_SYNTH)
-            throw std::runtime_error("synth_rollout_alloc first");
-        if (use_graph && reset) {
-            if (!roll_graph_exec) {
-                HIP_CHECK(hipStreamBeginCapture(
-                    stream, hipStreamCaptureModeThreadLocal));
-                synth_enqueue_episode(true);
-                HIP_CHECK(hipStreamEndCapture(stream, &roll_graph));
-                HIP_CHECK(hipGraphInstantiate(&roll_graph_exec, roll_graph,
-                                              nullptr, nullptr, 0));
-            }
-            for (int e = 0; e < episodes; ++e)
-                HIP_CHECK(hipGraphLaunch(roll_graph_exec, stream));
-        } else {
-            for (int e = 0; e < episodes; ++e)
-                synth_enqueue_episode(reset);
-        }
-        HIP_CHECK(hipStreamSynchronize(stream));
-    }
-
-    // the per-episode device words: [0] philox epoch, [1] replay base
-    void synth_rollout_words(long long (&w)[2]) {
-        if (roll_kind_ != ROLL_SYNTH)
-            throw std::runtime_error("synth_rollout_alloc first");
-        HIP_CHECK(hipMemcpy(w, syn_.ep_state, sizeof(w),
-                            hipMemcpyDeviceToHost));
+        roll_require(ROLL_SYNTH, "synth_rollout_alloc first");
+        run_episodes(episodes, reset, use_graph);
     }
 
     // test hook: inject exact env state, leaving the OU process as

@@ -19,30 +19,20 @@
 
 namespace d4pg {
 
-struct GoalRollArgs {
-    int M, D, n, horizon;
-    float gamma, eps, ou_theta, ou_sigma, ou_mu, ou_dt;
+// ep_state words past the core's [0..2]: [3] successes, [4] env steps (sum
+// of lengths); [5..7] rows, successes and env steps summed over the episodes
+// of one run call
+struct GoalRollArgs : RollCore {
+    int D;
     float speed, tol, her_ratio;
-    int noise_kind;                    // 0 = gaussian, 1 = OU
-    uint64_t seed;
-    float per_alpha;
-    // env + noise state: pos/goal/act/ou_x [M][D], obs [M][2D] = pos ‖ goal
-    float *pos, *goal, *obs, *act, *ou_x;
+    // env state: pos/goal [M][D]; the core's obs is [M][2D] = pos ‖ goal
+    float *pos, *goal;
     int *alive, *len, *succ;           // [M]
     // episode buffers: ep_pos [horizon+1][M][D], ep_act [horizon][M][D]
     float *ep_pos, *ep_act;
     // rows per env and their exclusive scan [M]
     int* count;
     long long* offset;
-    // per-episode device words: [0] philox epoch, [1] replay base pos,
-    // [2] rows emitted, [3] successes, [4] env steps (sum of lengths);
-    // [5..7] the same three summed over the episodes of one run call
-    long long* ep_state;
-    // replay
-    float *rs, *ra, *rr, *rs2, *rd;
-    double *sum_tree, *min_tree;
-    long tree_cap, capacity;
-    Counters* cnt;
 };
 
 // sparse reward of GoalReachEnv.compute_reward: 0 within tol, else -1
@@ -67,14 +57,6 @@ __device__ inline bool goal_her_draw(const GoalRollArgs& a, long long ep,
                         ((uint64_t)ep << 20) | (uint64_t)t, (uint64_t)i);
     fut = t + (int)(w.v[1] % (uint32_t)(T - t));
     return u01(w.v[0]) <= a.her_ratio;
-}
-
-// episode prologue: bump the philox epoch, latch the replay write base
-__global__ void k_goal_begin(GoalRollArgs a) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        a.ep_state[0] += 1;
-        a.ep_state[1] = a.cnt->pos;
-    }
 }
 
 // reset all M envs: pos and goal uniform in [-1,1]^D, OU state to mu, and
@@ -112,25 +94,9 @@ __global__ void k_goal_tick(GoalRollArgs a, int tick) {
          i += gridDim.x * blockDim.x) {
         if (!a.alive[i]) continue;
         for (int k = 0; k < D; ++k) {
-            // --- exploration noise, as k_roll_tick; dim k draws its own
-            // stream through the high half of ctr_lo ---
-            float u = a.act[i * D + k];
-            if (a.noise_kind == 0 && a.eps != 0.0f) {
-                Philox4 r = philox4(a.seed ^ 0x2F01Eull,
-                                    ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
-                                    ((uint64_t)k << 32) | (uint64_t)i);
-                u += a.eps * n01(r.v[0], r.v[1]);
-            } else if (a.noise_kind == 1) {
-                Philox4 r = philox4(a.seed ^ 0x2F01Eull,
-                                    ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
-                                    ((uint64_t)k << 32) | (uint64_t)i);
-                float x = a.ou_x[i * D + k];
-                x += a.ou_theta * (a.ou_mu - x) * a.ou_dt
-                     + a.ou_sigma * sqrtf(a.ou_dt) * n01(r.v[0], r.v[1]);
-                a.ou_x[i * D + k] = x;
-                u += a.eps * x;
-            }
-            u = fminf(fmaxf(u, -1.0f), 1.0f);
+            const float u = roll_explore(
+                a, ep, tick, ((uint64_t)k << 32) | (uint64_t)i,
+                a.act[i * D + k], a.ou_x + i * D + k);
             a.ep_act[((long)tick * M + i) * D + k] = u;
 
             // --- GoalReachEnv._step ---
@@ -230,8 +196,7 @@ void k_goal_emit(GoalRollArgs a) {
     const int lane = threadIdx.x & 63;
     const int wpb = blockDim.x >> 6;
     const long long ep = a.ep_state[0], base = a.ep_state[1];
-    const double pa = a.sum_tree
-        ? per_leaf_value(a.cnt->max_priority, a.per_alpha) : 0.0;
+    const double pa = roll_leaf_value(a);
     const int D = a.D, M = a.M, O = 2 * a.D;
     for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < M;
          i += gridDim.x * wpb) {
@@ -265,10 +230,7 @@ void k_goal_emit(GoalRollArgs a) {
             }
             a.rr[dst] = R;
             a.rd[dst] = (t == T - 1 && succ) ? 1.0f : 0.0f;
-            if (a.sum_tree) {                   // null: uniform replay
-                a.sum_tree[a.tree_cap + dst] = pa;
-                a.min_tree[a.tree_cap + dst] = pa;
-            }
+            roll_write_leaf(a, dst, pa);
         }
 
         // --- HER rows (one-step): (pos_t‖g', a_t, r', pos_{t+1}‖g',
@@ -297,10 +259,7 @@ void k_goal_emit(GoalRollArgs a) {
                 }
                 a.rr[dst] = r;
                 a.rd[dst] = r == 0.0f ? 1.0f : 0.0f;
-                if (a.sum_tree) {
-                    a.sum_tree[a.tree_cap + dst] = pa;
-                    a.min_tree[a.tree_cap + dst] = pa;
-                }
+                roll_write_leaf(a, dst, pa);
             }
             hits_before += __popcll(m);
         }
@@ -310,10 +269,8 @@ void k_goal_emit(GoalRollArgs a) {
 // episode epilogue: advance the replay counters by the device-side total
 __global__ void k_goal_end(GoalRollArgs a) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        long long base = a.ep_state[1], total = a.ep_state[2];
-        a.cnt->pos = (base + total) % a.capacity;
-        long long sz = a.cnt->size + total;
-        a.cnt->size = sz > a.capacity ? a.capacity : sz;
+        const long long total = a.ep_state[2];
+        roll_advance(a, total);
         a.ep_state[5] += total;
         a.ep_state[6] += a.ep_state[3];
         a.ep_state[7] += a.ep_state[4];

@@ -1,7 +1,8 @@
 // Device rollout kernels: M vectorized Pendulum envs, exploration noise and the
 // n-step fold, writing transitions straight into the on-HBM replay.  Used by
 // Engine::rollout_* (GPU actor ranks); the policy forward between ticks is
-// k_fwd below 512 envs and k_mfma_fwd from 512 up.
+// k_fwd below 512 envs and k_mfma_fwd from 512 up.  The episode prologue and
+// epilogue, the noise and the leaf write are engine_rollcore.hip's.
 
 namespace d4pg {
 
@@ -29,40 +30,12 @@ __device__ inline float d4pg_angle_norm(float x) {
     return y - PI;
 }
 
-// standard normal via Box-Muller on two philox lanes
-__device__ inline float n01(uint32_t a, uint32_t b) {
-    float u1 = u01(a), u2 = u01(b);
-    u1 = fmaxf(u1, 1e-12f);
-    return sqrtf(-2.0f * logf(u1)) *
-           cosf(6.283185307179586f * u2);
-}
-
-struct RollArgs {
-    int M, O, A, n, horizon;
-    float gamma, eps, ou_theta, ou_sigma, ou_mu, ou_dt;
-    int noise_kind;                    // 0 = gaussian, 1 = OU
-    uint64_t seed;
-    float per_alpha;
-    // env + noise state
-    float *th, *thdot, *obs, *act, *ou_x;
+struct RollArgs : RollCore {
+    int O, A;
+    float *th, *thdot;                 // env state [M]
     // n-step rings [n][M][*]
     float *s_ring, *a_ring, *r_ring;
-    // per-episode device state: [0] philox epoch, [1] replay base pos
-    long long* ep_state;
-    // replay
-    float *rs, *ra, *rr, *rs2, *rd;
-    double *sum_tree, *min_tree;
-    long tree_cap, capacity;
-    Counters* cnt;
 };
-
-// episode prologue: bump the philox epoch, latch the replay write base
-__global__ void k_roll_begin(RollArgs a) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        a.ep_state[0] += 1;
-        a.ep_state[1] = a.cnt->pos;
-    }
-}
 
 // reset all M envs (uniform th in [-pi,pi], thdot in [-1,1] — Pendulum-v1
 // reset distribution) + OU state to mu, and emit the first observation
@@ -90,28 +63,11 @@ __global__ void k_roll_tick(RollArgs a, int tick, int slot, int emit_k,
                             int done) {
     long long ep = a.ep_state[0];
     long long base = a.ep_state[1];
-    double pa = a.sum_tree
-        ? per_leaf_value(a.cnt->max_priority, a.per_alpha) : 0.0;
+    double pa = roll_leaf_value(a);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.M;
          i += gridDim.x * blockDim.x) {
-        // --- exploration noise (K11): per-env per-tick philox stream ---
-        float u_n = a.act[i * a.A];        // policy output, tanh in (-1,1)
-        if (a.noise_kind == 0 && a.eps != 0.0f) {
-            Philox4 r = philox4(a.seed ^ 0x2F01Eull,
-                                ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
-                                (uint64_t)i);
-            u_n += a.eps * n01(r.v[0], r.v[1]);
-        } else if (a.noise_kind == 1) {
-            Philox4 r = philox4(a.seed ^ 0x2F01Eull,
-                                ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
-                                (uint64_t)i);
-            float x = a.ou_x[i * a.A];
-            x += a.ou_theta * (a.ou_mu - x) * a.ou_dt
-                 + a.ou_sigma * sqrtf(a.ou_dt) * n01(r.v[0], r.v[1]);
-            a.ou_x[i * a.A] = x;
-            u_n += a.eps * x;
-        }
-        u_n = fminf(fmaxf(u_n, -1.0f), 1.0f);
+        float u_n = roll_explore(a, ep, tick, (uint64_t)i, a.act[i * a.A],
+                                 a.ou_x + i * a.A);
 
         // --- n-step ring: store s_t, a_t BEFORE stepping ---
         a.s_ring[(slot * a.M + i) * 3 + 0] = a.obs[i * 3 + 0];
@@ -156,21 +112,8 @@ __global__ void k_roll_tick(RollArgs a, int tick, int slot, int emit_k,
             a.rs2[dst * 3 + 1] = o1;
             a.rs2[dst * 3 + 2] = o2;
             a.rd[dst] = (float)done;
-            if (a.sum_tree) {                   // null: uniform replay
-                a.sum_tree[a.tree_cap + dst] = pa;
-                a.min_tree[a.tree_cap + dst] = pa;
-            }
+            roll_write_leaf(a, dst, pa);
         }
-    }
-}
-
-// episode epilogue: advance the replay counters by the emitted block
-__global__ void k_roll_end(RollArgs a, long emitted) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        long long base = a.ep_state[1];
-        a.cnt->pos = (base + emitted) % a.capacity;
-        long long sz = a.cnt->size + emitted;
-        a.cnt->size = sz > a.capacity ? a.capacity : sz;
     }
 }
 

@@ -10,46 +10,20 @@
 // general strides.  Per tick: the policy chain obs -> act, k_syn_act (noise,
 // clip, ring write), the mixing GEMM z = [obs ‖ act_env] . [W; U] through the
 // engine's own forward kernels, then k_syn_tick (process noise, tanh, reward,
-// fold and emit).
-//
-// Philox keys of the rollout streams (seed ^ constant; ctr_hi = (episode <<
-// 20) | sub-stream, ctr_lo = (dim << 32) | env):
-//   0xD011E  reset state          sub-stream 1          (all rollouts)
-//   0x2F01E  exploration noise    sub-stream tick + 2   (all rollouts)
-//   0x4E12E  HER draw             sub-stream t          (goal rollout)
-//   0x51A7E  process noise        sub-stream tick + 2   (this file)
+// fold and emit).  The episode prologue and epilogue, the exploration noise,
+// the leaf write and the table of philox keys are engine_rollcore.hip's.
 
 namespace d4pg {
 
-struct SynRollArgs {
-    int M, O, A, n, horizon;
-    float gamma, eps, ou_theta, ou_sigma, ou_mu, ou_dt;
+struct SynRollArgs : RollCore {
+    int O, A;
     float act_high, proc_sigma;
-    int noise_kind;                    // 0 = gaussian, 1 = OU
-    uint64_t seed;
-    float per_alpha;
-    // env + noise state: obs [M][O] (the env state IS the observation),
-    // act [M][A] policy output, act_env [M][A] = clipped noisy action *
-    // act_high, z [M][O] mixing GEMM output, ou_x [M][A]
-    float *obs, *act, *act_env, *z, *ou_x;
+    // env state: the core's obs [M][O] IS the env state; act_env [M][A] =
+    // clipped noisy action * act_high, z [M][O] mixing GEMM output
+    float *act_env, *z;
     // n-step rings: s_ring [n][M][O], a_ring [n][M][A], r_ring [n][M]
     float *s_ring, *a_ring, *r_ring;
-    // per-episode device state: [0] philox epoch, [1] replay base pos
-    long long* ep_state;
-    // replay
-    float *rs, *ra, *rr, *rs2, *rd;
-    double *sum_tree, *min_tree;
-    long tree_cap, capacity;
-    Counters* cnt;
 };
-
-// episode prologue: bump the philox epoch, latch the replay write base
-__global__ void k_syn_begin(SynRollArgs a) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        a.ep_state[0] += 1;
-        a.ep_state[1] = a.cnt->pos;
-    }
-}
 
 // reset all M envs: state 0.1 * N(0,1) per dim (SyntheticEnv._reset), OU
 // state to mu
@@ -67,11 +41,9 @@ __global__ void k_syn_reset(SynRollArgs a) {
     for (long e = t0; e < (long)a.M * a.A; e += stride) a.ou_x[e] = a.ou_mu;
 }
 
-// after the policy forward: exploration noise as k_goal_tick draws it ->
-// clip -> the NORMALIZED action into the ring, the scaled one to the env;
-// s_t into the ring before the env steps.  eps == 0 skips the Gaussian
-// draw; the OU state advances whatever eps is (it is state, and eps only
-// scales what is added), as in the other two rollouts.
+// after the policy forward: exploration noise -> clip -> the NORMALIZED
+// action into the ring, the scaled one to the env; s_t into the ring before
+// the env steps
 __global__ void k_syn_act(SynRollArgs a, int tick, int slot) {
     const long long ep = a.ep_state[0];
     const int M = a.M, O = a.O, A = a.A;
@@ -79,23 +51,9 @@ __global__ void k_syn_act(SynRollArgs a, int tick, int slot) {
     const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
     for (long e = t0; e < (long)M * A; e += stride) {
         const int i = (int)(e / A), k = (int)(e % A);
-        float u = a.act[e];                // policy output, tanh in (-1,1)
-        if (a.noise_kind == 0 && a.eps != 0.0f) {
-            Philox4 r = philox4(a.seed ^ 0x2F01Eull,
-                                ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
-                                ((uint64_t)k << 32) | (uint64_t)i);
-            u += a.eps * n01(r.v[0], r.v[1]);
-        } else if (a.noise_kind == 1) {
-            Philox4 r = philox4(a.seed ^ 0x2F01Eull,
-                                ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
-                                ((uint64_t)k << 32) | (uint64_t)i);
-            float x = a.ou_x[e];
-            x += a.ou_theta * (a.ou_mu - x) * a.ou_dt
-                 + a.ou_sigma * sqrtf(a.ou_dt) * n01(r.v[0], r.v[1]);
-            a.ou_x[e] = x;
-            u += a.eps * x;
-        }
-        u = fminf(fmaxf(u, -1.0f), 1.0f);
+        const float u = roll_explore(
+            a, ep, tick, ((uint64_t)k << 32) | (uint64_t)i, a.act[e],
+            a.ou_x + e);
         a.a_ring[(long)slot * M * A + e] = u;
         a.act_env[e] = u * a.act_high;
     }
@@ -113,8 +71,7 @@ void k_syn_tick(SynRollArgs a, int tick, int slot, int emit_k, int done) {
     const int lane = threadIdx.x & 63;
     const int wpb = blockDim.x >> 6;
     const long long ep = a.ep_state[0], base = a.ep_state[1];
-    const double pa = (emit_k >= 0 && a.sum_tree)
-        ? per_leaf_value(a.cnt->max_priority, a.per_alpha) : 0.0;
+    const double pa = emit_k >= 0 ? roll_leaf_value(a) : 0.0;
     const int M = a.M, O = a.O, A = a.A, n = a.n;
     const int start = (slot + 1) % n;           // oldest ring entry
     for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < M;
@@ -166,22 +123,9 @@ void k_syn_tick(SynRollArgs a, int tick, int slot, int emit_k, int done) {
                 R += gk * r;
                 a.rr[dst] = R;
                 a.rd[dst] = (float)done;
-                if (a.sum_tree) {               // null: uniform replay
-                    a.sum_tree[a.tree_cap + dst] = pa;
-                    a.min_tree[a.tree_cap + dst] = pa;
-                }
+                roll_write_leaf(a, dst, pa);
             }
         }
-    }
-}
-
-// episode epilogue: advance the replay counters by the emitted block
-__global__ void k_syn_end(SynRollArgs a, long emitted) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        long long base = a.ep_state[1];
-        a.cnt->pos = (base + emitted) % a.capacity;
-        long long sz = a.cnt->size + emitted;
-        a.cnt->size = sz > a.capacity ? a.capacity : sz;
     }
 }
 

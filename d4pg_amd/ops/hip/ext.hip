@@ -296,15 +296,19 @@ static void rollout_set_state(int64_t h, torch::Tensor th,
                         (int)t1.numel());
 }
 
-static py::dict rollout_info(int64_t h) {
-    Engine& e = get(h);
+// what the info dicts of the two static-count rollouts share
+static py::dict static_rollout_info(const RollCore& c) {
     py::dict d;
-    d["M"] = e.roll_.M;
-    d["n"] = e.roll_.n;
-    d["horizon"] = e.roll_.horizon;
-    d["emits_per_episode"] = (long)e.roll_emits_per_ep * e.roll_.M;
-    d["env_steps_per_episode"] = (long)e.roll_.horizon * e.roll_.M;
+    d["M"] = c.M;
+    d["n"] = c.n;
+    d["horizon"] = c.horizon;
+    d["emits_per_episode"] = (long)(c.horizon - c.n + 1) * c.M;
+    d["env_steps_per_episode"] = (long)c.horizon * c.M;
     return d;
+}
+
+static py::dict rollout_info(int64_t h) {
+    return static_rollout_info(get(h).roll_);
 }
 
 // ---- GPU-resident goal rollout + HER relabel (engine_goal.hip) ----
@@ -342,8 +346,9 @@ static void goal_rollout_set_state(int64_t h, torch::Tensor pos,
 
 static py::dict goal_rollout_info(int64_t h) {
     Engine& e = get(h);
+    e.roll_require(Engine::ROLL_GOAL, "goal_rollout_alloc first");
     long long w[5];
-    e.goal_rollout_words(w);
+    e.rollout_words(w);
     py::dict d;
     d["M"] = e.goal_.M;
     d["D"] = e.goal_.D;
@@ -362,8 +367,7 @@ static py::dict goal_rollout_info(int64_t h) {
 // test hook: the last episode as recorded on the device
 static py::dict goal_rollout_episode(int64_t h) {
     Engine& e = get(h);
-    long long w[5];
-    e.goal_rollout_words(w);            // throws unless a goal rollout is up
+    e.roll_require(Engine::ROLL_GOAL, "goal_rollout_alloc first");
     const GoalRollArgs& a = e.goal_;
     const long M = a.M, D = a.D, HOR = a.horizon;
     auto f32 = [&](const float* src, std::vector<int64_t> shape) {
@@ -424,16 +428,12 @@ static void synth_rollout_set_state(int64_t h, torch::Tensor state) {
 
 static py::dict synth_rollout_info(int64_t h) {
     Engine& e = get(h);
-    long long w[2];
-    e.synth_rollout_words(w);           // throws unless a synth rollout is up
-    py::dict d;
-    d["M"] = e.syn_.M;
+    e.roll_require(Engine::ROLL_SYNTH, "synth_rollout_alloc first");
+    long long w[5];
+    e.rollout_words(w);
+    py::dict d = static_rollout_info(e.syn_);
     d["O"] = e.syn_.O;
     d["A"] = e.syn_.A;
-    d["n"] = e.syn_.n;
-    d["horizon"] = e.syn_.horizon;
-    d["emits_per_episode"] = (long)e.syn_emits_per_ep * e.syn_.M;
-    d["env_steps_per_episode"] = (long)e.syn_.horizon * e.syn_.M;
     d["episode"] = (int64_t)w[0];
     d["base"] = (int64_t)w[1];
     return d;
@@ -466,25 +466,9 @@ static py::tuple replay_slice(int64_t h, int64_t base, int64_t count) {
 
 // (base, rows) of the last rollout episode, of any kind
 static py::tuple rollout_last(int64_t h) {
-    Engine& e = get(h);
-    if (e.roll_kind_ == Engine::ROLL_GOAL) {
-        long long w[5];
-        e.goal_rollout_words(w);
-        return py::make_tuple((int64_t)w[1], (int64_t)w[2]);
-    }
-    if (e.roll_kind_ == Engine::ROLL_SYNTH) {
-        long long w[2];
-        e.synth_rollout_words(w);
-        return py::make_tuple((int64_t)w[1],
-                              (int64_t)e.syn_emits_per_ep * e.syn_.M);
-    }
-    if (e.roll_kind_ != Engine::ROLL_PENDULUM)
-        throw std::runtime_error("no rollout allocated");
-    long long w[2];
-    HIP_CHECK(hipMemcpy(w, e.roll_.ep_state, sizeof(w),
-                        hipMemcpyDeviceToHost));
-    return py::make_tuple((int64_t)w[1],
-                          (int64_t)e.roll_emits_per_ep * e.roll_.M);
+    long long w[5];
+    get(h).rollout_words(w);
+    return py::make_tuple((int64_t)w[1], (int64_t)w[2]);
 }
 
 static torch::Tensor actor_forward(int64_t h, torch::Tensor x) {

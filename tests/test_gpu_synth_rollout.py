@@ -429,6 +429,87 @@ def test_refusals():
 
 
 # ---------------------------------------------------------------------------
+# one pool and one episode graph, handed from producer to producer
+# ---------------------------------------------------------------------------
+
+def _life_engine(o, like=None):
+    """(o, 1) engine with an 11-atom critic; `like`: take its four slabs."""
+    from d4pg_amd.models import critic
+    from d4pg_amd.ops import FusedEngine
+    eng = FusedEngine(obs_dim=o, act_dim=1, hidden=H, n_atoms=11, batch=64,
+                      capacity=64, v_min=-10.0, v_max=1.0,
+                      gamma_n=GAMMA ** 2, tau=0.001, lr_actor=1e-4,
+                      lr_critic=1e-4, seed=0)
+    if like is None:
+        torch.manual_seed(NET_SEED)
+        c = critic(o, 1, dict(DIST, n_atoms=11), hidden=H)
+        eng.load_from_modules(_net(o, 1), _net(o, 1), c, c)
+    else:
+        for name in ("actor", "actor_target", "critic", "critic_target"):
+            eng.load_slab(name, like.store_slab(name))
+    return eng
+
+
+@pytest.mark.parametrize("kind", ["pendulum", "goal"])
+def test_pool_and_graph_across_kinds(kind):
+    """kind -> synth -> kind on one engine, every episode graph-captured:
+    each allocation frees the previous producer's pool and graph, so what an
+    episode writes is bitwise what an engine that ran only that step writes
+    (the captured run resets the envs from the seed, after the injected
+    state).  Pendulum's third episode wraps the 64-slot ring; the goal
+    rollout's row counts depend on the episodes."""
+    o = 3 if kind == "pendulum" else 2
+    m, n, hor = 5, 2, 6
+    vec = _twin(o, 1, m, hor)
+    x0 = np.linspace(-0.8, 0.8, m, dtype=np.float32)
+
+    def own(eng, seed):
+        if kind == "pendulum":
+            eng.rollout_alloc(m, n, horizon=hor, gamma=GAMMA, seed=seed)
+            eng.rollout_set_state(2 * x0, x0[::-1].copy())
+            return eng.rollout_run(1, reset=True, use_graph=True)
+        eng.goal_rollout_alloc(m, n, horizon=hor, gamma=GAMMA, tol=0.3,
+                               seed=seed)
+        eng.goal_rollout_set_state(x0[:, None], -x0[:, None])
+        return eng.goal_rollout_run(1, reset=True, use_graph=True)
+
+    def synth(eng):
+        eng.synth_rollout_alloc(m, n, vec.W, vec.U, horizon=hor, gamma=GAMMA,
+                                seed=SEED)
+        return eng.synth_rollout_run(1, reset=True, use_graph=True)
+
+    eng = _life_engine(o)
+    own(eng, seed=21)
+    first = eng.counters()["pos"]
+    assert synth(eng) == (m * hor, m * (hor - n + 1))
+    only_synth = _life_engine(o, like=eng)
+    synth(only_synth)
+    rows = eng.rollout_last_rows()
+    assert len(rows[2]) == m * (hor - n + 1)
+    assert eng.synth_rollout_info()["base"] == first > 0
+    for g, w in zip(rows, only_synth.rollout_last_rows()):
+        assert np.array_equal(g, w)
+    with pytest.raises(RuntimeError, match="rollout_alloc first"):
+        eng.rollout_run(1)
+    with pytest.raises(RuntimeError, match="goal_rollout_alloc first"):
+        eng.goal_rollout_run(1)
+
+    before = eng.counters()["pos"]
+    out = own(eng, seed=22)
+    only_last = _life_engine(o, like=eng)
+    assert own(only_last, seed=22) == out
+    rows = eng.rollout_last_rows()
+    assert len(rows[2]) == out[1] > 0
+    if kind == "pendulum":                          # 50 + 25 rows: wraps
+        assert before + out[1] > 64
+    assert eng.counters()["pos"] == (before + out[1]) % 64
+    for g, w in zip(rows, only_last.rollout_last_rows()):
+        assert np.array_equal(g, w)
+    with pytest.raises(RuntimeError, match="synth_rollout_alloc first"):
+        eng.synth_rollout_run(1)
+
+
+# ---------------------------------------------------------------------------
 # the learner trains on what the rollout wrote
 # ---------------------------------------------------------------------------
 
