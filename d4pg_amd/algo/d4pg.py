@@ -138,7 +138,7 @@ class DDPG:
     @property
     def engine(self):
         """The fused HIP engine bridge (backend='hip' after the first
-        train step), else None."""
+        train step or ensure_engine()), else None."""
         return self._fused
 
     # ------------------------------------------------------------------
@@ -312,11 +312,20 @@ class DDPG:
         self.train_steps_done += 1
         return float(qdist_loss.detach()), float(policy_loss.detach())
 
-    def _train_step_hip(self):
+    def ensure_engine(self):
+        """Build the fused HIP engine bridge now (backend='hip') instead of on
+        the first train step, and return it: the device collect/evaluate path
+        of the Worker needs the engine during warm-up.  Idempotent."""
+        if self.backend != "hip":
+            raise RuntimeError("ensure_engine: backend is %r, not 'hip'"
+                               % self.backend)
         if self._fused is None:
             from ..ops import build_fused_engine
             self._fused = build_fused_engine(self)
-        return self._fused.step()
+        return self._fused
+
+    def _train_step_hip(self):
+        return self.ensure_engine().step()
 
     # ------------------------------------------------------------------
     # checkpointing

@@ -93,7 +93,13 @@ def make_parser() -> argparse.ArgumentParser:
                    help="MI355X extension: batch M vectorized envs per "
                         "actor rank (one [M,obs] policy forward per tick) "
                         "instead of one env per process; 0 = scalar parity "
-                        "mode (distributed learner only)")
+                        "mode.  On one GPU (backend hip, --gpu_actors != 0, "
+                        "Pendulum / GoalReach --her 1 / synthetic envs) the "
+                        "Worker collects and evaluates with M-env device "
+                        "episodes on the learner's engine: --warmup and "
+                        "--episodes_per_cycle then round UP to whole "
+                        "batches of M episodes, ceil(episodes / M) device "
+                        "episodes each")
     p.add_argument("--gpu_actors", default=-1, type=int,
                    help="device-resident rollout for vector actor ranks "
                         "(env dynamics + policy + noise + n-step fold as "

@@ -21,6 +21,10 @@ from .core import Box, Env
 
 
 class SyntheticEnv(Env):
+    # scale of the process noise in _step; the vector twin and the device
+    # rollouts that model this env take it from here
+    proc_sigma = 0.01
+
     def __init__(self, obs_dim: int, act_dim: int, horizon: int = 1000,
                  act_high: float = 1.0, seed: int | None = None):
         super().__init__(seed)
@@ -43,7 +47,8 @@ class SyntheticEnv(Env):
     def _step(self, action):
         a = np.clip(action, self.action_space.low, self.action_space.high)
         self.state = np.tanh(self.state @ self.W + a @ self.U
-                             + 0.01 * self.rng.standard_normal(self.obs_dim))
+                             + self.proc_sigma
+                             * self.rng.standard_normal(self.obs_dim))
         reward = float(-np.mean(self.state ** 2) + 0.1 * np.mean(a ** 2))
         return self.state.astype(np.float32).copy(), reward, False, {}
 

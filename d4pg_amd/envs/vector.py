@@ -330,3 +330,80 @@ class VectorSynthetic:
                   + f(0.1) * np.mean(u ** 2, axis=1)).astype(f)
         self.t += 1
         return self.state.copy(), reward, self.t >= self.horizon
+
+
+def vector_evaluate(actor, vec_env, episodes: int = 1, reset: bool = True):
+    """Greedy evaluation over a vector env: ``episodes`` noise-free episodes
+    of all ``vec_env.n`` envs under ``actor`` (a torch module mapping
+    [M, obs] to [M, act], or an agent holding one as ``.actor``), the action
+    being clip(actor(obs), -1, 1).  Dynamics are the twins' own float32
+    update order; the undiscounted returns are summed in float64 in tick
+    order.
+
+    Returns ``(summary, (ret, len, succ))``: summary is the dict
+    ``FusedEngine.evaluate`` returns (mean_return, min_return, max_return,
+    success_rate, env_steps, episodes) over all env episodes of the call, and
+    the arrays are per env for the LAST episode (float64, int32, int32).
+    Host twin of the device evaluation (ops/hip/engine_eval.hip): it is what
+    the CPU path calls, and the device path's parity oracle when the env's
+    start states and process noise come from the philox sources.
+
+    ``reset=False`` starts the first episode from the state the env already
+    holds (after ``set_state``, or th / thdot / t set by hand), which is how
+    the tests inject start states; later episodes always reset."""
+    import torch
+
+    if isinstance(vec_env, VectorGoalReach):
+        kind = "goal"
+    elif isinstance(vec_env, (VectorPendulum, VectorSynthetic)):
+        kind = "sync"
+    else:
+        raise TypeError(
+            "vector_evaluate: unsupported vector env %s (VectorPendulum, "
+            "VectorGoalReach or VectorSynthetic)" % type(vec_env).__name__)
+    episodes = int(episodes)
+    if episodes < 1:
+        raise ValueError("vector_evaluate: episodes < 1")
+    net = getattr(actor, "actor", actor)
+    m, horizon = vec_env.n, vec_env.horizon
+
+    def policy(obs):
+        with torch.no_grad():
+            a = net(torch.from_numpy(np.ascontiguousarray(obs, np.float32)))
+        return np.clip(a.numpy(), -1.0, 1.0).astype(np.float32)
+
+    total = 0.0
+    lo, hi = np.inf, -np.inf
+    n_succ = n_steps = 0
+    for ep in range(episodes):
+        if reset or ep > 0:
+            obs = vec_env.reset()
+        elif isinstance(vec_env, VectorSynthetic):
+            obs = vec_env.state.copy()
+        else:
+            obs = vec_env._obs()
+        ret = np.zeros(m, np.float64)
+        succ = np.zeros(m, np.int32)
+        if kind == "goal":
+            for _ in range(horizon):
+                live = vec_env.alive.copy()
+                if not live.any():
+                    break
+                obs, r, _, _ = vec_env.step(policy(obs))
+                ret[live] += r[live].astype(np.float64)
+            length = vec_env.len.astype(np.int32)
+            succ = vec_env.succ.astype(np.int32)
+        else:
+            for _ in range(horizon):
+                obs, r, _ = vec_env.step(policy(obs))
+                ret += np.asarray(r, np.float64)
+            length = np.full(m, horizon, np.int32)
+        total += float(np.sum(ret, dtype=np.float64))
+        lo, hi = min(lo, float(ret.min())), max(hi, float(ret.max()))
+        n_succ += int(succ.sum())
+        n_steps += int(length.sum())
+    count = m * episodes
+    summary = dict(mean_return=total / count, min_return=lo, max_return=hi,
+                   success_rate=n_succ / count, env_steps=n_steps,
+                   episodes=episodes)
+    return summary, (ret, length, succ)

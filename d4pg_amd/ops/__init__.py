@@ -417,6 +417,66 @@ class FusedEngine:
     def synth_rollout_info(self):
         return self.ext.synth_rollout_info(self.h)
 
+    # -- device greedy evaluation (ops/hip/engine_eval.hip): noise-free
+    # episodes of the allocated rollout producer's env, in a pool of their
+    # own; nothing training reads is written --
+    def eval_alloc(self, n_envs, horizon=None, seed=None, fixed_starts=False):
+        """Allocate `n_envs` evaluation envs of the allocated rollout's kind
+        (call after a *_rollout_alloc; a new one drops the evaluation).
+        horizon None: the rollout's.  seed None: the rollout seed ^
+        0x5EEDE7A1.  fixed_starts: every episode starts from the same states
+        (and process noise), for common random numbers across checkpoints."""
+        self.ext.eval_alloc(self.h, int(n_envs),
+                            0 if horizon is None else int(horizon),
+                            seed is not None,
+                            0 if seed is None else int(seed),
+                            bool(fixed_starts))
+
+    def evaluate(self, episodes=1, use_graph=True):
+        """Run `episodes` greedy episodes over the evaluation envs (one
+        hipGraph launch each) and read the reduced result back in one copy."""
+        episodes = int(episodes)
+        if episodes < 1:
+            raise ValueError("evaluate: episodes < 1")
+        self.ext.eval_run(self.h, episodes, bool(use_graph))
+        r = self.ext.eval_results(self.h)
+        n = int(r["count"])
+        return dict(mean_return=float(r["sum"]) / n,
+                    min_return=float(r["min"]), max_return=float(r["max"]),
+                    success_rate=int(r["successes"]) / n,
+                    env_steps=int(r["env_steps"]), episodes=episodes)
+
+    def eval_returns(self):
+        """(ret float64, len int32, succ int32) per env of the last
+        evaluation episode."""
+        ret, ln, succ = self.ext.eval_arrays(self.h)
+        return ret.numpy(), ln.numpy(), succ.numpy()
+
+    # test hooks of the evaluation (tests/test_gpu_eval.py); not part of the
+    # product surface
+    def eval_results(self):
+        """Test hook: the raw result words of the last evaluate() call."""
+        return dict(self.ext.eval_results(self.h))
+
+    def eval_set_state(self, x, y=None):
+        """Test hook: start the next evaluation episode from the given env
+        state — (th, thdot) for Pendulum, (pos, goal) for GoalReach, (state,)
+        for the synthetic envs."""
+        x = torch.as_tensor(np.asarray(x, np.float32))
+        y = (torch.zeros(0) if y is None
+             else torch.as_tensor(np.asarray(y, np.float32)))
+        self.ext.eval_set_state(self.h, x, y)
+
+    def eval_info(self):
+        """Test hook: E, horizon, seed and fixed_starts as eval_alloc
+        settled them."""
+        return dict(self.ext.eval_info(self.h))
+
+    def rollout_words(self):
+        """Test hook: the eight per-episode device words of the allocated
+        rollout."""
+        return self.ext.rollout_words(self.h).numpy()
+
     def rollout_last_rows(self):
         """Host copy of the rows of the LAST rollout episode only, in write
         order, from its replay base and row count (replay_rows() returns

@@ -31,6 +31,7 @@
 #include "engine_rollout.hip"
 #include "engine_goal.hip"
 #include "engine_synth.hip"
+#include "engine_eval.hip"
 #include "engine_mfma.hip"
 #include "engine_persistent.hip"
 
@@ -867,6 +868,7 @@ public:
     }
 
     void rollout_free() {
+        eval_free();                    // the evaluation models this producer
         if (roll_graph_exec) { hipGraphExecDestroy(roll_graph_exec);
                                roll_graph_exec = nullptr; }
         if (roll_graph) { hipGraphDestroy(roll_graph); roll_graph = nullptr; }
@@ -927,6 +929,12 @@ public:
 
     // the policy forward obs [M][obs] -> act [M][act] between two ticks
     void roll_fwd_chain(const float* obs, float* act, int M) {
+        roll_fwd_chain(obs, act, M, r_h1, r_h2, r_h3);
+    }
+
+    // the same chain over hidden buffers [M][hidden] of the caller's
+    void roll_fwd_chain(const float* obs, float* act, int M, float* h1,
+                        float* h2, float* h3) {
         // (the tanh head takes the plain MFMA launch here, not the split-K
         // head pair: dw_parts is sized for the learner batch, not for M)
         auto run = [&](const float* x, const LayerDesc& l, float* y,
@@ -935,10 +943,10 @@ public:
             if (fwd_uses_mfma(M)) launch_fwd_mfma(j);
             else launch_fwd_valu(j);
         };
-        run(obs, anet.l[0], r_h1, ACT_RELU);
-        run(r_h1, anet.l[1], r_h2, ACT_NONE);   // fc2->fc2_2 no-act quirk
-        run(r_h2, anet.l[2], r_h3, ACT_RELU);
-        run(r_h3, anet.l[3], act, ACT_TANH);
+        run(obs, anet.l[0], h1, ACT_RELU);
+        run(h1, anet.l[1], h2, ACT_NONE);       // fc2->fc2_2 no-act quirk
+        run(h2, anet.l[2], h3, ACT_RELU);
+        run(h3, anet.l[3], act, ACT_TANH);
     }
 
     // one whole episode of the allocated producer, on the engine's stream
@@ -1244,6 +1252,249 @@ public:
         std::vector<float> ou((long)M * syn_.A, syn_.ou_mu);
         HIP_CHECK(hipMemcpy(syn_.ou_x, ou.data(), ou.size() * 4,
                             hipMemcpyHostToDevice));
+    }
+
+    // ---------------- greedy evaluation (engine_eval.hip) ----------------
+    // E noise-free envs of the allocated producer's kind, with that
+    // producer's env parameters, in a pool of their own (hidden buffers of
+    // the policy chain included): nothing training reads is written.  One
+    // episode is one single-stream hipGraph, captured on first use after
+    // eval_alloc.  rollout_free(), and with it every *_rollout_alloc, drops
+    // the evaluation: it models the producer that was allocated.
+    EvalArgs eval_{};
+    void* eval_pool_ = nullptr;
+    float *e_h1 = nullptr, *e_h2 = nullptr, *e_h3 = nullptr;
+    hipGraph_t eval_graph = nullptr;
+    hipGraphExec_t eval_graph_exec = nullptr;
+    // eval_set_state ran: the next episode starts from what it injected
+    bool eval_injected_ = false;
+
+    void eval_free() {
+        if (eval_graph_exec) { hipGraphExecDestroy(eval_graph_exec);
+                               eval_graph_exec = nullptr; }
+        if (eval_graph) { hipGraphDestroy(eval_graph); eval_graph = nullptr; }
+        if (eval_pool_) { hipFree(eval_pool_); eval_pool_ = nullptr; }
+        eval_injected_ = false;
+    }
+
+    void eval_require() {
+        if (!eval_pool_) throw std::runtime_error("eval_alloc first");
+    }
+
+    // horizon 0: the rollout's; has_seed false: the rollout seed ^ 0x5EEDE7A1
+    void eval_alloc(int E, int horizon, bool has_seed, uint64_t seed,
+                    bool fixed_starts) {
+        if (roll_kind_ == ROLL_NONE)
+            throw std::runtime_error(
+                "eval_alloc: no rollout allocated (the evaluation models the "
+                "allocated producer's env)");
+        if (E < 1 || E > 65536)
+            throw std::runtime_error("eval_alloc: n_envs not in [1, 65536]");
+        const RollCore& c = roll_core();
+        if (horizon == 0) horizon = c.horizon;
+        if (horizon < 1 || horizon >= (1 << 20) - 2)
+            throw std::runtime_error(
+                "eval_alloc: horizon not in [1, 2^20 - 2)");
+        eval_free();
+        EvalArgs a{};
+        a.E = E; a.horizon = horizon; a.fixed_starts = fixed_starts ? 1 : 0;
+        a.seed = has_seed ? seed : (c.seed ^ 0x5EEDE7A1ull);
+        const int O = cfg.obs, A = cfg.act;
+        a.O = O; a.A = A; a.D = A;
+        if (roll_kind_ == ROLL_GOAL) {
+            a.speed = goal_.speed; a.tol = goal_.tol;
+        } else if (roll_kind_ == ROLL_SYNTH) {
+            a.act_high = syn_.act_high; a.proc_sigma = syn_.proc_sigma;
+        }
+        char* base = nullptr;
+        long off = 0;
+        auto sub = [&](auto*& p, long nelem) {      // nelem in 4-byte words
+            if (base) p = reinterpret_cast<decltype(+p)>(base + off);
+            off += (nelem * 4 + 255) & ~255L;
+        };
+        auto carve_all = [&] {
+            off = 0;
+            sub(a.obs, (long)E * O); sub(a.act, (long)E * A);
+            sub(a.ret, 2L * E); sub(a.len, E); sub(a.succ, E);
+            sub(a.words, 2L * (EVAL_WORDS + 1));
+            if (roll_kind_ == ROLL_PENDULUM) {
+                sub(a.th, E); sub(a.thdot, E);
+            } else if (roll_kind_ == ROLL_GOAL) {
+                sub(a.pos, (long)E * A); sub(a.goal, (long)E * A);
+                sub(a.alive, E);
+            } else {
+                sub(a.act_env, (long)E * A); sub(a.z, (long)E * O);
+            }
+            const long EH = (long)E * cfg.hidden;
+            sub(e_h1, EH); sub(e_h2, EH); sub(e_h3, EH);
+        };
+        carve_all();
+        HIP_CHECK(hipMalloc(&eval_pool_, off));
+        HIP_CHECK(hipMemset(eval_pool_, 0, off));
+        base = (char*)eval_pool_;
+        carve_all();
+        // every episode of a fixed-starts evaluation is episode 1; otherwise
+        // k_eval_begin moves 0 on to 1 before the first one
+        const long long epoch0 = fixed_starts ? 1 : 0;
+        HIP_CHECK(hipMemcpy(a.words + EVAL_EPOCH, &epoch0, 8,
+                            hipMemcpyHostToDevice));
+        HIP_CHECK(hipDeviceSynchronize());
+        eval_ = a;
+    }
+
+    void eval_enqueue_episode(bool reset) {
+        EvalArgs& a = eval_;
+        const int E = a.E;
+        int wgs = ceil_div(E, 256);
+        hipLaunchKernelGGL(k_eval_begin, dim3(1), dim3(64), 0, stream, a);
+        auto chain = [&] {
+            roll_fwd_chain(a.obs, a.act, E, e_h1, e_h2, e_h3);
+        };
+        if (roll_kind_ == ROLL_PENDULUM) {
+            if (reset)
+                hipLaunchKernelGGL(k_eval_pend_reset, dim3(wgs), dim3(256), 0,
+                                   stream, a);
+            for (int t = 0; t < a.horizon; ++t) {
+                chain();
+                hipLaunchKernelGGL(k_eval_pend_tick, dim3(wgs), dim3(256), 0,
+                                   stream, a, t);
+            }
+        } else if (roll_kind_ == ROLL_GOAL) {
+            if (reset)
+                hipLaunchKernelGGL(k_eval_goal_reset, dim3(wgs), dim3(256), 0,
+                                   stream, a);
+            for (int t = 0; t < a.horizon; ++t) {
+                chain();
+                hipLaunchKernelGGL(k_eval_goal_tick, dim3(wgs), dim3(256), 0,
+                                   stream, a, t);
+            }
+        } else {
+            const long elems = (long)E * (a.O > a.A ? a.O : a.A);
+            int ewgs = ceil_div(elems, 256);
+            if (ewgs > 2048) ewgs = 2048;
+            int twgs = ceil_div(E, 4);          // one wave per env
+            if (twgs > 2048) twgs = 2048;
+            if (reset)
+                hipLaunchKernelGGL(k_eval_syn_reset, dim3(ewgs), dim3(256), 0,
+                                   stream, a);
+            FwdJob mix = fwd_job(a.obs, a.act_env, syn_dyn_, syn_dyn_desc_,
+                                 a.z, ACT_NONE, E);
+            for (int t = 0; t < a.horizon; ++t) {
+                chain();
+                hipLaunchKernelGGL(k_eval_syn_act, dim3(ewgs), dim3(256), 0,
+                                   stream, a);
+                if (fwd_uses_mfma(E)) launch_fwd_mfma(mix);
+                else launch_fwd_valu(mix);
+                hipLaunchKernelGGL(k_eval_syn_tick, dim3(twgs), dim3(256), 0,
+                                   stream, a, t);
+            }
+        }
+        hipLaunchKernelGGL(k_eval_reduce, dim3(1),
+                           dim3(EVAL_REDUCE_THREADS), 0, stream, a);
+    }
+
+    // `episodes` evaluation episodes; the result words sum over them
+    void eval_run(int episodes, bool use_graph) {
+        eval_require();
+        if (episodes < 1)
+            throw std::runtime_error(
+                "eval_run: episodes < 1 (the result words would count no "
+                "env episode)");
+        HIP_CHECK(hipMemsetAsync(eval_.words, 0, EVAL_WORDS * 8, stream));
+        for (int e = 0; e < episodes; ++e) {
+            if (eval_injected_) {
+                eval_injected_ = false;
+                eval_enqueue_episode(false);
+            } else if (use_graph) {
+                if (!eval_graph_exec) {
+                    HIP_CHECK(hipStreamBeginCapture(
+                        stream, hipStreamCaptureModeThreadLocal));
+                    eval_enqueue_episode(true);
+                    HIP_CHECK(hipStreamEndCapture(stream, &eval_graph));
+                    HIP_CHECK(hipGraphInstantiate(&eval_graph_exec,
+                                                  eval_graph, nullptr,
+                                                  nullptr, 0));
+                }
+                HIP_CHECK(hipGraphLaunch(eval_graph_exec, stream));
+            } else {
+                eval_enqueue_episode(true);
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+
+    struct EvalResults {
+        double sum, min, max;
+        long long successes, env_steps, count, episode, episodes;
+    };
+    static_assert(sizeof(EvalResults) == EVAL_WORDS * 8, "result words");
+
+    // the one 64-byte device-to-host copy of an evaluation
+    EvalResults eval_results() {
+        eval_require();
+        EvalResults r{};
+        HIP_CHECK(hipMemcpy(&r, eval_.words, sizeof(r),
+                            hipMemcpyDeviceToHost));
+        return r;
+    }
+
+    // per-env results of the last episode
+    void eval_arrays(double* ret, int* len, int* succ) {
+        eval_require();
+        const long E = eval_.E;
+        HIP_CHECK(hipMemcpy(ret, eval_.ret, E * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(len, eval_.len, E * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(succ, eval_.succ, E * 4, hipMemcpyDeviceToHost));
+    }
+
+    // test hook: inject exact env state for the next episode, leaving
+    // everything else as the evaluation reset leaves it.  Pendulum: x = th,
+    // y = thdot [E]; GoalReach: x = pos, y = goal [E][D]; synthetic: x =
+    // state [E][obs], y unused.
+    void eval_set_state(const float* x, const float* y, long nx, long ny) {
+        eval_require();
+        EvalArgs& a = eval_;
+        const long E = a.E;
+        auto up = [&](void* dst, const void* src, long bytes) {
+            HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        };
+        if (roll_kind_ == ROLL_PENDULUM) {
+            if (nx != E || ny != E)
+                throw std::runtime_error("eval_set_state: th/thdot not [E]");
+            std::vector<float> obs(3 * E);
+            for (long i = 0; i < E; ++i) {
+                obs[i * 3 + 0] = cosf(x[i]);
+                obs[i * 3 + 1] = sinf(x[i]);
+                obs[i * 3 + 2] = y[i];
+            }
+            up(a.th, x, E * 4); up(a.thdot, y, E * 4);
+            up(a.obs, obs.data(), 3 * E * 4);
+        } else if (roll_kind_ == ROLL_GOAL) {
+            const long D = a.D, ED = E * D;
+            if (nx != ED || ny != ED)
+                throw std::runtime_error("eval_set_state: pos/goal not [E][D]");
+            std::vector<float> obs(2 * ED);
+            for (long i = 0; i < E; ++i)
+                for (long k = 0; k < D; ++k) {
+                    obs[i * 2 * D + k] = x[i * D + k];
+                    obs[i * 2 * D + D + k] = y[i * D + k];
+                }
+            std::vector<int> alive(E, 1);
+            up(a.pos, x, ED * 4); up(a.goal, y, ED * 4);
+            up(a.obs, obs.data(), 2 * ED * 4);
+            up(a.alive, alive.data(), E * 4);
+        } else {
+            if (nx != E * a.O)
+                throw std::runtime_error("eval_set_state: state not [E][obs]");
+            up(a.obs, x, E * a.O * 4);
+        }
+        HIP_CHECK(hipMemset(a.ret, 0, E * 8));
+        HIP_CHECK(hipMemset(a.len, 0, E * 4));
+        HIP_CHECK(hipMemset(a.succ, 0, E * 4));
+        // the clears went to the null stream; the episode kernels run on
+        // the engine's non-blocking stream
+        HIP_CHECK(hipDeviceSynchronize());
+        eval_injected_ = true;
     }
 
     // actor forward for eval/smoke: x[B,obs] (device via staging) -> a[B,act]

@@ -46,6 +46,30 @@ __device__ inline float goal_reward(const float* p, const float* g, int D,
     return sqrtf(d2) <= tol ? 0.0f : -1.0f;
 }
 
+// The env step, in one copy for the training tick below and the evaluation
+// tick (engine_eval.hip): GoalReachEnv._step's move and clip of one dim under
+// the clipped action u, and the success test on the stored position, which
+// is the test the emit's rewards use.
+__device__ inline float goal_move(float p, float speed, float u) {
+    p = p + speed * u;
+    return fminf(fmaxf(p, -1.0f), 1.0f);
+}
+
+__device__ inline bool goal_reached(const float* p, const float* g, int D,
+                                    float tol) {
+    return goal_reward(p, g, D, tol) == 0.0f;
+}
+
+// Reset draw of dim k of env i at episode ep: pos and goal uniform in
+// [-1, 1], shared with the evaluation reset.
+__device__ inline void goal_reset_draw(uint64_t seed, long long ep, int i,
+                                       int k, float& p, float& g) {
+    Philox4 r = philox4(seed ^ 0xD011Eull, ((uint64_t)ep << 20) | 1u,
+                        ((uint64_t)k << 32) | (uint64_t)i);
+    p = 2.0f * u01(r.v[0]) - 1.0f;
+    g = 2.0f * u01(r.v[1]) - 1.0f;
+}
+
 // HER draw of step t of env i (T = the env's episode length, t < T): whether
 // the step gets a hindsight row and, if so, the future index in [t, T) whose
 // achieved position becomes the goal.  u01 is in (0,1], so a ratio of 1
@@ -67,11 +91,8 @@ __global__ void k_goal_reset(GoalRollArgs a) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.M;
          i += gridDim.x * blockDim.x) {
         for (int k = 0; k < D; ++k) {
-            Philox4 r = philox4(a.seed ^ 0xD011Eull,
-                                ((uint64_t)ep << 20) | 1u,
-                                ((uint64_t)k << 32) | (uint64_t)i);
-            float p = 2.0f * u01(r.v[0]) - 1.0f;
-            float g = 2.0f * u01(r.v[1]) - 1.0f;
+            float p, g;
+            goal_reset_draw(a.seed, ep, i, k, p, g);
             a.pos[i * D + k] = p;
             a.goal[i * D + k] = g;
             a.obs[i * 2 * D + k] = p;
@@ -100,15 +121,14 @@ __global__ void k_goal_tick(GoalRollArgs a, int tick) {
             a.ep_act[((long)tick * M + i) * D + k] = u;
 
             // --- GoalReachEnv._step ---
-            float p = a.pos[i * D + k] + a.speed * u;
-            p = fminf(fmaxf(p, -1.0f), 1.0f);
+            const float p = goal_move(a.pos[i * D + k], a.speed, u);
             a.pos[i * D + k] = p;
             a.obs[i * 2 * D + k] = p;
             a.ep_pos[((long)(tick + 1) * M + i) * D + k] = p;
         }
         a.len[i] = tick + 1;
         // the same test the emit's rewards use, on the stored position
-        if (goal_reward(a.pos + i * D, a.goal + i * D, D, a.tol) == 0.0f) {
+        if (goal_reached(a.pos + i * D, a.goal + i * D, D, a.tol)) {
             a.succ[i] = 1;
             a.alive[i] = 0;
         }

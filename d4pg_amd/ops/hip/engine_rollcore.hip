@@ -11,6 +11,12 @@
 //   0x2F01E  exploration noise    sub-stream tick + 2   (roll_explore)
 //   0x4E12E  HER draw             sub-stream t          (goal rollout)
 //   0x51A7E  process noise        sub-stream tick + 2   (synth rollout)
+// The greedy evaluation (engine_eval.hip) draws from the same table with its
+// own seed, seed_eval = rollout seed ^ 0x5EEDE7A1 unless eval_alloc sets
+// another, and its own epoch word in place of `episode`: reset states from
+// seed_eval ^ 0xD011E sub-stream 1, the synth process noise from seed_eval ^
+// 0x51A7E; it has no exploration and no HER draw.  With fixed starts the
+// epoch stays at 1; otherwise it advances once per evaluation episode.
 
 namespace d4pg {
 

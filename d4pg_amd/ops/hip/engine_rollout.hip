@@ -30,6 +30,33 @@ __device__ inline float d4pg_angle_norm(float x) {
     return y - PI;
 }
 
+// Reset draw of env i at episode ep (Pendulum-v1 reset distribution: th
+// uniform in [-pi, pi], thdot in [-1, 1]); the training reset and the
+// evaluation reset (engine_eval.hip) both call it with their own seed.
+__device__ inline void pendulum_reset_draw(uint64_t seed, long long ep, int i,
+                                           float& th, float& td) {
+    Philox4 r = philox4(seed ^ 0xD011Eull, ((uint64_t)ep << 20) | 1u,
+                        (uint64_t)i);
+    th = (2.0f * u01(r.v[0]) - 1.0f) * 3.14159265358979f;
+    td = 2.0f * u01(r.v[1]) - 1.0f;
+}
+
+// One env step (VectorPendulum.step parity) under the clipped normalized
+// action u_n: advances (th, td) in place and returns the reward -cost.  The
+// one copy of the dynamics; the training tick below and the evaluation tick
+// call it.
+__device__ inline float pendulum_step(float u_n, float& th, float& td) {
+    const float max_torque = 2.0f, max_speed = 8.0f, dt = 0.05f, g = 10.0f;
+    float u = u_n * max_torque;
+    float an = d4pg_angle_norm(th);
+    float cost = an * an + 0.1f * td * td + 0.001f * u * u;
+    float newtd = td + (1.5f * g * sinf(th) + 3.0f * u) * dt;
+    newtd = fminf(fmaxf(newtd, -max_speed), max_speed);
+    th = th + newtd * dt;
+    td = newtd;
+    return -cost;
+}
+
 struct RollArgs : RollCore {
     int O, A;
     float *th, *thdot;                 // env state [M]
@@ -43,10 +70,8 @@ __global__ void k_roll_reset(RollArgs a) {
     long long ep = a.ep_state[0];
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.M;
          i += gridDim.x * blockDim.x) {
-        Philox4 r = philox4(a.seed ^ 0xD011Eull, ((uint64_t)ep << 20) | 1u,
-                            (uint64_t)i);
-        float th = (2.0f * u01(r.v[0]) - 1.0f) * 3.14159265358979f;
-        float td = 2.0f * u01(r.v[1]) - 1.0f;
+        float th, td;
+        pendulum_reset_draw(a.seed, ep, i, th, td);
         a.th[i] = th;
         a.thdot[i] = td;
         a.obs[i * 3 + 0] = cosf(th);
@@ -76,19 +101,12 @@ __global__ void k_roll_tick(RollArgs a, int tick, int slot, int emit_k,
         a.a_ring[slot * a.M + i] = u_n;
 
         // --- Pendulum dynamics (VectorPendulum.step parity) ---
-        const float max_torque = 2.0f, max_speed = 8.0f, dt = 0.05f,
-                    g = 10.0f;
         float th = a.th[i], td = a.thdot[i];
-        float u = u_n * max_torque;
-        float an = d4pg_angle_norm(th);
-        float cost = an * an + 0.1f * td * td + 0.001f * u * u;
-        float newtd = td + (1.5f * g * sinf(th) + 3.0f * u) * dt;
-        newtd = fminf(fmaxf(newtd, -max_speed), max_speed);
-        th = th + newtd * dt;
+        const float r = pendulum_step(u_n, th, td);
         a.th[i] = th;
-        a.thdot[i] = newtd;
-        a.r_ring[slot * a.M + i] = -cost;
-        float o0 = cosf(th), o1 = sinf(th), o2 = newtd;
+        a.thdot[i] = td;
+        a.r_ring[slot * a.M + i] = r;
+        float o0 = cosf(th), o1 = sinf(th), o2 = td;
         a.obs[i * 3 + 0] = o0;
         a.obs[i * 3 + 1] = o1;
         a.obs[i * 3 + 2] = o2;

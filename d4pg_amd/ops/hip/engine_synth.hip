@@ -25,6 +25,52 @@ struct SynRollArgs : RollCore {
     float *s_ring, *a_ring, *r_ring;
 };
 
+// Reset draw of dim k of env i at episode ep: 0.1 * N(0,1)
+// (SyntheticEnv._reset), shared with the evaluation reset (engine_eval.hip).
+__device__ inline float syn_reset_draw(uint64_t seed, long long ep, int i,
+                                       int k) {
+    Philox4 r = philox4(seed ^ 0xD011Eull, ((uint64_t)ep << 20) | 1u,
+                        ((uint64_t)k << 32) | (uint64_t)i);
+    return 0.1f * n01(r.v[0], r.v[1]);
+}
+
+// SyntheticEnv._step of env i by one wave, after the mixing GEMM left z:
+// s' = tanh(z + sigma * N(0,1)) into the env's obs row (and into s2_row, the
+// replay's next-state row, when non-null), then r = -mean(s'^2) +
+// 0.1 * mean(act_env^2) by two wave sums, returned on every lane.  Lanes
+// stride over the dims, so every O-wide row access is coalesced.  The one
+// copy of the dynamics: the training tick below and the evaluation tick call
+// it, each with its own seed.
+__device__ inline float syn_env_step(const float* z, float* obs, float* s2_row,
+                                     const float* act_env, int O, int A,
+                                     float proc_sigma, uint64_t seed,
+                                     long long ep, int tick, int i, int lane) {
+    float ss = 0.0f;
+    for (int k = lane; k < O; k += 64) {
+        float zz = z[k];
+        if (proc_sigma != 0.0f) {
+            Philox4 r = philox4(seed ^ 0x51A7Eull,
+                                ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
+                                ((uint64_t)k << 32) | (uint64_t)i);
+            zz += proc_sigma * n01(r.v[0], r.v[1]);
+        }
+        const float s2 = tanhf(zz);
+        obs[k] = s2;
+        if (s2_row) s2_row[k] = s2;
+        ss += s2 * s2;
+    }
+    float sa = 0.0f;
+    for (int k = lane; k < A; k += 64) {
+        const float u = act_env[k];
+        sa += u * u;
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        ss += __shfl_xor(ss, s, 64);
+        sa += __shfl_xor(sa, s, 64);
+    }
+    return -ss / (float)O + 0.1f * sa / (float)A;
+}
+
 // reset all M envs: state 0.1 * N(0,1) per dim (SyntheticEnv._reset), OU
 // state to mu
 __global__ void k_syn_reset(SynRollArgs a) {
@@ -34,9 +80,7 @@ __global__ void k_syn_reset(SynRollArgs a) {
     const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
     for (long e = t0; e < (long)a.M * O; e += stride) {
         const int i = (int)(e / O), k = (int)(e % O);
-        Philox4 r = philox4(a.seed ^ 0xD011Eull, ((uint64_t)ep << 20) | 1u,
-                            ((uint64_t)k << 32) | (uint64_t)i);
-        a.obs[e] = 0.1f * n01(r.v[0], r.v[1]);
+        a.obs[e] = syn_reset_draw(a.seed, ep, i, k);
     }
     for (long e = t0; e < (long)a.M * a.A; e += stride) a.ou_x[e] = a.ou_mu;
 }
@@ -79,31 +123,10 @@ void k_syn_tick(SynRollArgs a, int tick, int slot, int emit_k, int done) {
         const long dst = emit_k >= 0
             ? (long)((base + (long long)emit_k * M + i) % a.capacity) : 0;
 
-        // --- SyntheticEnv._step: s' = tanh(z + sigma * N(0,1)) ---
-        float ss = 0.0f;
-        for (int k = lane; k < O; k += 64) {
-            float zz = a.z[(long)i * O + k];
-            if (a.proc_sigma != 0.0f) {
-                Philox4 r = philox4(a.seed ^ 0x51A7Eull,
-                                    ((uint64_t)ep << 20) | (uint64_t)(tick + 2),
-                                    ((uint64_t)k << 32) | (uint64_t)i);
-                zz += a.proc_sigma * n01(r.v[0], r.v[1]);
-            }
-            const float s2 = tanhf(zz);
-            a.obs[(long)i * O + k] = s2;
-            if (emit_k >= 0) a.rs2[dst * O + k] = s2;
-            ss += s2 * s2;
-        }
-        float sa = 0.0f;
-        for (int k = lane; k < A; k += 64) {
-            const float u = a.act_env[(long)i * A + k];
-            sa += u * u;
-        }
-        for (int s = 32; s > 0; s >>= 1) {
-            ss += __shfl_xor(ss, s, 64);
-            sa += __shfl_xor(sa, s, 64);
-        }
-        const float r = -ss / (float)O + 0.1f * sa / (float)A;
+        const float r = syn_env_step(
+            a.z + (long)i * O, a.obs + (long)i * O,
+            emit_k >= 0 ? a.rs2 + dst * O : nullptr, a.act_env + (long)i * A,
+            O, A, a.proc_sigma, a.seed, ep, tick, i, lane);
         if (lane == 0) a.r_ring[(long)slot * M + i] = r;
 
         // --- matured n-step emit (VecNStep parity): transition

@@ -439,6 +439,67 @@ static py::dict synth_rollout_info(int64_t h) {
     return d;
 }
 
+// ---- device greedy evaluation (engine_eval.hip) ----
+static void eval_alloc(int64_t h, int64_t E, int64_t horizon, bool has_seed,
+                       int64_t seed, bool fixed_starts) {
+    // range checks before the narrowing casts
+    if (E < 1 || E > 65536)
+        throw std::runtime_error("eval_alloc: n_envs not in [1, 65536]");
+    if (horizon < 0 || horizon >= (1 << 20) - 2)
+        throw std::runtime_error("eval_alloc: horizon not in [1, 2^20 - 2)");
+    get(h).eval_alloc((int)E, (int)horizon, has_seed, (uint64_t)seed,
+                      fixed_starts);
+}
+
+static void eval_run(int64_t h, int64_t episodes, bool use_graph) {
+    get(h).eval_run((int)episodes, use_graph);
+}
+
+static py::dict eval_results(int64_t h) {
+    Engine::EvalResults r = get(h).eval_results();
+    py::dict d;
+    d["sum"] = r.sum;
+    d["min"] = r.min;
+    d["max"] = r.max;
+    d["successes"] = (int64_t)r.successes;
+    d["env_steps"] = (int64_t)r.env_steps;
+    d["count"] = (int64_t)r.count;
+    d["episode"] = (int64_t)r.episode;
+    d["episodes"] = (int64_t)r.episodes;
+    return d;
+}
+
+// per-env (ret float64, len int32, succ int32) of the last episode
+static py::tuple eval_arrays(int64_t h) {
+    Engine& e = get(h);
+    e.eval_require();
+    const int64_t E = e.eval_.E;
+    auto ret = torch::empty({E}, torch::kFloat64);
+    auto len = torch::empty({E}, torch::kInt32);
+    auto succ = torch::empty({E}, torch::kInt32);
+    e.eval_arrays(ret.data_ptr<double>(), len.data_ptr<int>(),
+                  succ.data_ptr<int>());
+    return py::make_tuple(ret, len, succ);
+}
+
+static void eval_set_state(int64_t h, torch::Tensor x, torch::Tensor y) {
+    auto t1 = f32_contig(x), t2 = f32_contig(y);
+    get(h).eval_set_state(t1.data_ptr<float>(), t2.data_ptr<float>(),
+                          t1.numel(), t2.numel());
+}
+
+// test hook: what eval_alloc settled on
+static py::dict eval_info(int64_t h) {
+    Engine& e = get(h);
+    e.eval_require();
+    py::dict d;
+    d["E"] = e.eval_.E;
+    d["horizon"] = e.eval_.horizon;
+    d["seed"] = e.eval_.seed;
+    d["fixed_starts"] = (bool)e.eval_.fixed_starts;
+    return d;
+}
+
 // Host copy of `count` replay rows starting at ring slot `base` (wrapping),
 // in ring order.
 static py::tuple replay_slice(int64_t h, int64_t base, int64_t count) {
@@ -469,6 +530,18 @@ static py::tuple rollout_last(int64_t h) {
     long long w[5];
     get(h).rollout_words(w);
     return py::make_tuple((int64_t)w[1], (int64_t)w[2]);
+}
+
+// test hook (the evaluation's no-side-effects check snapshots them): all
+// eight per-episode device words of the allocated rollout
+static torch::Tensor rollout_words(int64_t h) {
+    Engine& e = get(h);
+    if (e.roll_kind_ == Engine::ROLL_NONE)
+        throw std::runtime_error("no rollout allocated");
+    auto t = torch::empty({8}, torch::kInt64);
+    HIP_CHECK(hipMemcpy(t.data_ptr<int64_t>(), e.roll_core().ep_state, 64,
+                        hipMemcpyDeviceToHost));
+    return t;
 }
 
 static torch::Tensor actor_forward(int64_t h, torch::Tensor x) {
@@ -579,6 +652,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("synth_rollout_run", &d4pg::synth_rollout_run);
     mod.def("synth_rollout_set_state", &d4pg::synth_rollout_set_state);
     mod.def("synth_rollout_info", &d4pg::synth_rollout_info);
+    mod.def("eval_alloc", &d4pg::eval_alloc);
+    mod.def("eval_run", &d4pg::eval_run);
+    mod.def("eval_results", &d4pg::eval_results);
+    mod.def("eval_arrays", &d4pg::eval_arrays);
+    mod.def("eval_set_state", &d4pg::eval_set_state);
+    mod.def("eval_info", &d4pg::eval_info);
+    mod.def("rollout_words", &d4pg::rollout_words);
     mod.def("replay_slice", &d4pg::replay_slice);
     mod.def("rollout_last", &d4pg::rollout_last);
     mod.def("actor_forward", &d4pg::actor_forward);

@@ -330,6 +330,20 @@ class DistributedD4PG:
                         ou_sigma=args.ou_sigma, ou_mu=args.ou_mu,
                         seed=seed + 37)
                     self.goal_engine = True
+        # evaluator rank with --vector_envs > 0: eval_trials greedy vector
+        # envs per round in place of one scalar episode — on a GPU (and
+        # --gpu_actors != 0) the device evaluation of an engine built like
+        # the actor ranks' (ops/hip/engine_eval.hip), else vector_evaluate
+        # over the host twin
+        self.vec_eval = None
+        if self.is_evaluator and int(getattr(args, "vector_envs", 0)) > 0:
+            from .vec_eval import VectorEvaluator, env_kind
+            kind = env_kind(args, self.env)
+            if kind is not None:
+                self.vec_eval = VectorEvaluator(
+                    args, self.env, kind, self.obs_dim, self.act_dim, seed,
+                    use_gpu=ga != 0 and torch.cuda.is_available(),
+                    hidden=self.agent.actor.hidden)
         self.blob_len = pack_net(self.agent.actor).numel() + 1
 
         self.grad_meter = Meter()
@@ -376,7 +390,10 @@ class DistributedD4PG:
         if self.is_learner:
             return lb
         if self.is_evaluator:
-            _, R, _ = rollout_episode(self.agent, self.env, noise=False)
+            if self.vec_eval is not None:
+                R, _ = self.vec_eval.evaluate(self.agent.actor)
+            else:
+                _, R, _ = rollout_episode(self.agent, self.env, noise=False)
             self.ewma = R if self.ewma is None else \
                 0.95 * self.ewma + 0.05 * R
             print(f"[eval] step {self.global_step} return {R:.2f} "

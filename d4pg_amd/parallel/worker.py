@@ -39,9 +39,76 @@ class Worker:
         self.env_meter = Meter()
         self.rng = np.random.default_rng(
             None if args.seed is None else args.seed + hash(self.name) % 1000)
+        self._device_run = None     # the allocated producer's run method
+        self.device_rows = 0        # replay rows the device episodes wrote
+        self._device_kind = self._find_device_kind()
+
+    # -- the closed on-GPU cycle --
+    # With backend 'hip', --vector_envs M > 0, --gpu_actors != 0 and an env
+    # one of the device rollouts models (Pendulum; GoalReach with --her 1; an
+    # env that unwraps to SyntheticEnv — the tests DistributedD4PG applies),
+    # collection and evaluation run as device episodes on the learner's OWN
+    # engine: rows go straight into the replay the fused step samples, the
+    # policy is the p_actor slab the step updates (no parameter copy, no host
+    # rows) and env.step is never called.  Episode counts round up to whole
+    # batches of M envs.
+    eval_fixed_starts = False   # common random numbers across evaluations
+
+    def _find_device_kind(self):
+        a = self.args
+        if getattr(self.agent, "backend", "eager") != "hip":
+            return None
+        if int(getattr(a, "vector_envs", 0)) <= 0 \
+                or int(getattr(a, "gpu_actors", -1)) == 0:
+            return None
+        from .vec_eval import env_kind
+        return env_kind(a, self.env)
+
+    def device_kind(self):
+        """'pendulum' / 'goal' / 'synth' when this Worker takes the device
+        path, else None (decided once, at construction)."""
+        return self._device_kind
+
+    def device_engine(self):
+        """The learner's engine with this env's rollout producer and the
+        evaluation allocated on it (built on first use)."""
+        if self._device_run is not None:
+            return self.agent.engine.engine
+        from .vec_eval import alloc_producer, producer_rows
+        a, kind = self.args, self._device_kind
+        m = int(a.vector_envs)
+        horizon = int(self.env._max_episode_steps)
+        need = producer_rows(kind, m, horizon, a.n_steps)
+        cap = int(getattr(self.agent, "memory_size", a.rmsize))
+        if cap < need:
+            raise ValueError(
+                "--rmsize %d is below the %d rows one device episode of "
+                "--vector_envs %d envs can write (M*(max_steps-n_steps+1)%s): "
+                "two rows of one episode would share a replay slot; raise "
+                "--rmsize or lower --vector_envs"
+                % (cap, need, m,
+                   " + M*max_steps hindsight rows" if kind == "goal" else ""))
+        eng = self.agent.ensure_engine().engine
+        seed = (0 if a.seed is None else int(a.seed)) + 37
+        self._device_run = alloc_producer(eng, kind, a, self.env, m, seed)
+        eng.eval_alloc(int(a.eval_trials), horizon=horizon,
+                       fixed_starts=self.eval_fixed_starts)
+        return eng
+
+    def _device_collect(self, episodes: int) -> None:
+        if episodes <= 0:
+            return
+        self.device_engine()
+        self.agent.replayBuffer.flush()
+        m = int(self.args.vector_envs)
+        out = self._device_run(-(-int(episodes) // m))
+        self.env_meter.add(int(out[0]))
+        self.device_rows += int(out[1])
 
     # -- warmup fill (reference main.py:200-243) --
     def warmup(self) -> None:
+        if self._device_kind is not None:
+            return self._device_collect(self.args.warmup)
         for _ in range(self.args.warmup):
             ep, _, _ = rollout_episode(self.agent, self.env, noise=True)
             self.env_meter.add(len(ep))
@@ -50,6 +117,8 @@ class Worker:
                            gamma=self.args.gamma, rng=self.rng)
 
     def collect_cycle(self) -> None:
+        if self._device_kind is not None:
+            return self._device_collect(self.args.episodes_per_cycle)
         for _ in range(self.args.episodes_per_cycle):
             ep, _, _ = rollout_episode(self.agent, self.env, noise=True)
             self.env_meter.add(len(ep))
@@ -75,6 +144,11 @@ class Worker:
                 global_count += 1     # HogWild-tolerated non-atomic increment
 
     def evaluate(self):
+        if self._device_kind is not None:
+            # eval_trials greedy device envs on the slab the step updates:
+            # no sync_params_if_dirty()
+            r = self.device_engine().evaluate(1)
+            return float(r["mean_return"]), float(r["success_rate"])
         returns, successes = [], []
         for _ in range(self.args.eval_trials):
             _, R, s = rollout_episode(self.agent, self.env, noise=False)

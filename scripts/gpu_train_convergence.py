@@ -3,7 +3,11 @@
 product path (Worker + fused HIP engine) and report eval returns per cycle.
 Random policy scores ~-1200..-1500; a learning agent reaches -150..-400.
 
-Usage: python scripts/gpu_train_convergence.py [cycles]
+Usage: python scripts/gpu_train_convergence.py [cycles] [--vector_envs M]
+
+With --vector_envs M > 0 (and a GPU) the Worker takes the closed on-GPU
+cycle: M-env device episodes collect into the learner's replay and the
+evaluation runs on the device; the host env is never stepped.
 """
 
 import os
@@ -19,14 +23,21 @@ from d4pg_amd.config import configure_env_params, make_parser  # noqa: E402
 from d4pg_amd.envs import make, obs_act_dims  # noqa: E402
 from d4pg_amd.parallel.worker import Worker  # noqa: E402
 
-cycles = int(sys.argv[1]) if len(sys.argv) > 1 else 30
+import argparse  # noqa: E402
+
+_cli = argparse.ArgumentParser()
+_cli.add_argument("cycles", nargs="?", type=int, default=30)
+_cli.add_argument("--vector_envs", type=int, default=0)
+_opts = _cli.parse_args()
+cycles = _opts.cycles
 
 args = make_parser().parse_args(
     ["--env", "Pendulum-v1", "--max_steps", "200", "--warmup", "5",
      "--rmsize", "1000000", "--bsize", "64", "--n_steps", "5",
      "--n_eps", "1000", "--cycles_per_epoch", "1000000", "--debug", "0",
      "--episodes_per_cycle", "8", "--train_steps_per_cycle", "600",
-     "--eval_trials", "3", "--seed", "0"])
+     "--eval_trials", "3", "--seed", "0",
+     "--vector_envs", str(_opts.vector_envs)])
 configure_env_params(args)
 
 env = make(args.env, seed=0)
@@ -52,6 +63,7 @@ for cyc in range(cycles):
     best = max(best, avg_r)
     print(f"cycle {cyc:3d}  t={time.perf_counter() - t0:6.1f}s  "
           f"grad_steps={agent.train_steps_done:6d}  "
+          f"env_steps_per_sec={w.env_meter.rate():9.0f}  "
           f"eval_return={avg_r:8.1f}  best={best:8.1f}", flush=True)
 print(f"FINAL best_eval_return {best:.1f} "
       f"({'LEARNING OK' if best > -700 else 'NOT CONVERGED'})")
