@@ -37,6 +37,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ..config import check_gemm_precision
 from ..models import actor as Actor, critic as Critic
 from ..noise import GaussianNoise
 from ..replay.uniform import Replay
@@ -52,7 +53,13 @@ class DDPG:
                  n_steps=1, *, device="cpu", backend="eager", hidden=256,
                  is_weighting=False, true_td_priorities=False, seed=None,
                  noise="gaussian", noise_eps=0.3, ou_theta=0.15,
-                 ou_sigma=0.2, ou_mu=0.0):
+                 ou_sigma=0.2, ou_mu=0.0, gemm_precision="fp32"):
+        check_gemm_precision(gemm_precision)
+        if gemm_precision == "bf16" and backend != "hip":
+            raise ValueError(
+                "gemm_precision='bf16' is a mode of the hip backend's wide "
+                "train step; the %r backend computes in fp32 only" % backend)
+        self.gemm_precision = gemm_precision
         self.gamma = gamma
         self.n_steps = n_steps
         self.n_step_gamma = gamma ** n_steps

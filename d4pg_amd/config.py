@@ -17,6 +17,17 @@ import os
 from dataclasses import dataclass, field
 
 
+# MFMA operand types of the hip backend's wide train step (--gemm_precision,
+# DDPG / FusedEngine gemm_precision=)
+GEMM_PRECISIONS = ("fp32", "bf16")
+
+
+def check_gemm_precision(value) -> None:
+    if value not in GEMM_PRECISIONS:
+        raise ValueError("gemm_precision must be one of %r, got %r"
+                         % (GEMM_PRECISIONS, value))
+
+
 def make_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="MI355X-native D4PG")
 
@@ -105,6 +116,13 @@ def make_parser() -> argparse.ArgumentParser:
                         "(env dynamics + policy + noise + n-step fold as "
                         "HIP kernels): 1 = force, 0 = off, -1 = auto "
                         "(on when the rank sees a GPU)")
+    p.add_argument("--gemm_precision", default="fp32", type=str,
+                   choices=list(GEMM_PRECISIONS),
+                   help="MFMA operand type of the hip backend's wide train "
+                        "step (--bsize > 512): 'bf16' rounds both GEMM "
+                        "operands to bf16 and accumulates in fp32; weights, "
+                        "Adam state and the replay stay fp32.  Refused by "
+                        "the eager backend and at --bsize <= 512")
     p.add_argument("--her_ratio", default=0.8, type=float,
                    help="probability that a step also stores a hindsight "
                         "('future' strategy) copy when --her 1")
@@ -202,6 +220,7 @@ class D4PGConfig:
     vector_envs: int = 0
     gpu_actors: int = -1
     her_ratio: float = 0.8
+    gemm_precision: str = "fp32"
     extra: dict = field(default_factory=dict)
 
     @classmethod

@@ -21,6 +21,8 @@ import os
 import numpy as np
 import torch
 
+from ..config import check_gemm_precision
+
 _EXT = None
 _EXT_ERR: Exception | None = None
 
@@ -180,12 +182,18 @@ class FusedEngine:
                  v_min, v_max, gamma_n, tau, lr_actor, lr_critic,
                  per_alpha=0.6, per_beta0=0.4, per_beta_iters=100000,
                  per_eps=1e-6, seed=0, is_weighting=False,
-                 prioritized=True, true_td_priorities=False):
+                 prioritized=True, true_td_priorities=False,
+                 gemm_precision="fp32"):
         """prioritized=False: uniform replay (an integer philox draw per
         probe, IS weights exactly 1, no sum/min trees allocated or
         maintained).  true_td_priorities: the written-back priority is
         |E_m[z] - E_q[z]| + per_eps in place of the reference's <m, q>
-        proxy."""
+        proxy.  gemm_precision="bf16": the GEMMs of the wide train step
+        (batch > 512) round both operands to bf16 and accumulate in fp32;
+        parameters, moments, activations and the replay stay fp32, and so do
+        the rollout and evaluation forwards (ARCHITECTURE.md, "bf16 wide
+        path").  The engine refuses it at batch <= 512."""
+        check_gemm_precision(gemm_precision)
         self.ext = load_extension()
         self.h = self.ext.create(
             obs_dim, act_dim, hidden, n_atoms, batch, capacity,
@@ -193,8 +201,9 @@ class FusedEngine:
             float(lr_actor), float(lr_critic), float(per_alpha),
             float(per_beta0), int(per_beta_iters), float(per_eps),
             int(seed), bool(is_weighting), bool(prioritized),
-            bool(true_td_priorities))
+            bool(true_td_priorities), gemm_precision == "bf16")
         self.batch = batch
+        self.gemm_precision = gemm_precision
         self.prioritized = bool(prioritized)
         self._captured = 0
         self._persistent = bool(self.ext.info(self.h).get("persistent", False))
@@ -518,6 +527,7 @@ class FusedDDPGBridge:
             is_weighting=ddpg.is_weighting,
             prioritized=ddpg.prioritized_replay,
             true_td_priorities=ddpg.true_td_priorities,
+            gemm_precision=ddpg.gemm_precision,
             seed=0 if ddpg.rng is None else int(ddpg.rng.integers(1 << 31)))
         self.engine.load_from_modules(ddpg.actor, ddpg.actor_target,
                                       ddpg.critic, ddpg.critic_target)

@@ -12,7 +12,8 @@
 // Three execution paths, selected by batch size (Engine::step_path):
 // PERSISTENT (B <= 256, engine_persistent.hip), ROW-BLOCK (256 < B <= 512
 // and every split step up to 512, engine_rowblock.hip) and WIDE (B > 512,
-// engine_mfma.hip + engine_layer.hip).  Forward-only work (actor_forward,
+// engine_mfma.hip + engine_layer.hip; with EngineCfg.gemm_bf16 its GEMMs take
+// the bf16-operand kernels of engine_mfma_bf16.hip).  Forward-only work (actor_forward,
 // the device rollout) takes the MFMA forward kernel from 512 rows up and
 // the VALU k_fwd below.
 //
@@ -33,6 +34,7 @@
 #include "engine_synth.hip"
 #include "engine_eval.hip"
 #include "engine_mfma.hip"
+#include "engine_mfma_bf16.hip"
 #include "engine_persistent.hip"
 
 namespace d4pg {
@@ -93,6 +95,11 @@ public:
             throw std::runtime_error("layer fan-in exceeds FWD_XMAX LDS tile");
         if (c.atoms > 64)
             throw std::runtime_error("n_atoms > 64 (softmax is wave-wide)");
+        if (c.gemm_bf16 && c.batch <= 512)
+            throw std::runtime_error(
+                "gemm_precision='bf16' needs batch > 512: only the wide "
+                "train step has bf16 GEMMs, the persistent and row-block "
+                "paths (batch <= 512) are fp32 only");
         anet = make_actor_net(c.obs, c.act, c.hidden);
         cnet = make_critic_net(c.obs, c.act, c.hidden, c.atoms);
         ws.B = c.batch; ws.O = c.obs; ws.A = c.act; ws.H = c.hidden;
@@ -341,9 +348,12 @@ public:
                            stream, j);
     }
 
-    void launch_fwd_mfma(const FwdJob& j) {
+    // bf16 (here and below): the bf16-operand twin of the kernel, same grid
+    // and arguments — only the wide train step in gemm_bf16 mode passes it.
+    void launch_fwd_mfma(const FwdJob& j, bool bf16 = false) {
         int ntm = ceil_div(j.B, MT_M), ntn = ceil_div(j.out, MT_N);
-        hipLaunchKernelGGL(k_mfma_fwd, dim3(ntm * ntn), dim3(256), 0, stream,
+        hipLaunchKernelGGL(bf16 ? k_mfma_fwd_bf16 : k_mfma_fwd,
+                           dim3(ntm * ntn), dim3(256), 0, stream,
                            j.x1, j.x2, j.wt, j.bias, j.y, j.B, j.in1, j.in2,
                            j.out, j.act, 1, (float*)nullptr);
     }
@@ -351,11 +361,12 @@ public:
     // Narrow head (out <= 64, incl. the softmax ones): split-K partials in
     // dw_parts + a wave-per-row finish — the M-tile-only grid of a plain
     // launch was chip-starved on both the VALU kernel (~60 us) and MFMA.
-    void launch_fwd_mfma_head(const FwdJob& j) {
+    void launch_fwd_mfma_head(const FwdJob& j, bool bf16 = false) {
         int ntm = ceil_div(j.B, MT_M);
         int ks = 1;
         while (ntm * ks < 512 && ks * 2 * MT_K <= j.in1 + j.in2) ks *= 2;
-        hipLaunchKernelGGL(k_mfma_fwd, dim3(ntm * ks), dim3(256), 0, stream,
+        hipLaunchKernelGGL(bf16 ? k_mfma_fwd_bf16 : k_mfma_fwd,
+                           dim3(ntm * ks), dim3(256), 0, stream,
                            j.x1, j.x2, j.wt, j.bias, j.y, j.B, j.in1, j.in2,
                            j.out, j.act, ks, dw_parts);
         if (ks > 1)
@@ -366,11 +377,15 @@ public:
 
     // Layers of one phase over the engine's batch (independent of each
     // other; launched back to back).
-    void launch_fwd(std::initializer_list<FwdJob> jobs) {
+    void launch_fwd(std::initializer_list<FwdJob> jobs, bool bf16 = false) {
         for (auto& j : jobs) {
-            if (!fwd_uses_mfma(j.B)) launch_fwd_valu(j);
-            else if (j.out <= 64) launch_fwd_mfma_head(j);
-            else launch_fwd_mfma(j);
+            if (!fwd_uses_mfma(j.B)) {
+                if (bf16)
+                    throw std::runtime_error("no bf16 form of k_fwd");
+                launch_fwd_valu(j);
+            }
+            else if (j.out <= 64) launch_fwd_mfma_head(j, bf16);
+            else launch_fwd_mfma(j, bf16);
         }
     }
 
@@ -381,8 +396,10 @@ public:
     void launch_bwd(const float* dz, const float* x1, const float* x2,
                     const float* slab, float* gslab, const LayerDesc& l,
                     float* dx1, float* dx2, const float* h1, int prev_act,
-                    bool want_dw) {
+                    bool want_dw, bool bf16 = false) {
         int in_total = l.in1 + l.in2;
+        auto k_dw = bf16 ? k_mfma_dw_bf16 : k_mfma_dw;
+        auto k_dx = bf16 ? k_mfma_dx_bf16 : k_mfma_dx;
         if (want_dw) {
             // split K (= batch) until the grid covers the chip; segments
             // write disjoint partials, k_dw_reduce sums (atomic epilogue
@@ -400,7 +417,7 @@ public:
                 while (ntm * ntn * ksplit < 256 &&
                        ksplit * 2 * MT_K <= cfg.batch)
                     ksplit *= 2;
-                hipLaunchKernelGGL(k_mfma_dw, dim3(ntm * ntn * ksplit),
+                hipLaunchKernelGGL(k_dw, dim3(ntm * ntn * ksplit),
                                    dim3(256), 0, stream, dz, xop,
                                    (const float*)nullptr, dwt, db,
                                    cfg.batch, in_n, 0, l.out, ksplit,
@@ -418,14 +435,15 @@ public:
         if (dx1) {
             int ntm = ceil_div(cfg.batch, MT_M);
             int ntn = ceil_div(l.in1, MT_N);
-            hipLaunchKernelGGL(k_mfma_dx, dim3(ntm * ntn), dim3(256), 0,
+            hipLaunchKernelGGL(k_dx, dim3(ntm * ntn), dim3(256), 0,
                                stream, dz, slab + l.w_off, h1, dx1,
                                cfg.batch, 0, l.in1, l.out, prev_act);
         }
         if (dx2) {
             if (l.in2 <= 8) {
                 // action slice: wave-per-row VALU beats a 1-N-tile MFMA
-                // grid by ~7x here (see k_dx_narrow comment)
+                // grid by ~7x here (see k_dx_narrow comment); fp32 in
+                // either precision mode
                 hipLaunchKernelGGL(k_dx_narrow, dim3(256), dim3(256), 0,
                                    stream, dz, slab + l.w_off,
                                    (const float*)nullptr, dx2, cfg.batch,
@@ -433,7 +451,7 @@ public:
             } else {
                 int ntm = ceil_div(cfg.batch, MT_M);
                 int ntn = ceil_div(l.in2, MT_N);
-                hipLaunchKernelGGL(k_mfma_dx, dim3(ntm * ntn), dim3(256),
+                hipLaunchKernelGGL(k_dx, dim3(ntm * ntn), dim3(256),
                                    0, stream, dz, slab + l.w_off,
                                    (const float*)nullptr, dx2, cfg.batch,
                                    l.in1, in_total, l.out, ACT_NONE);
@@ -555,6 +573,9 @@ public:
     void enqueue_step_wide(int mask) {
         const int B = cfg.batch, K = cfg.atoms;
         const int waves_per_wg = 4;
+        // every GEMM below (launch_fwd / launch_bwd) takes bf16 operands in
+        // gemm_bf16 mode; the VALU kernels between them stay fp32
+        const bool bf = cfg.gemm_bf16 != 0;
         int row_wgs = ceil_div(B, waves_per_wg);
 
         if (mask & PH_CRITIC_GRADS) {
@@ -565,29 +586,29 @@ public:
                     fwd_job(ws.bs2, nullptr, ws.p_critic_t, cnet.l[0], ws.ct_h1,
                             ACT_RELU),
                     fwd_job(ws.bs, nullptr, ws.p_critic, cnet.l[0], ws.c_h1,
-                            ACT_RELU)});
+                            ACT_RELU)}, bf);
         // P3: a_t.L2 | c.L2(cat c_h1, a)
         launch_fwd({fwd_job(ws.at_h1, nullptr, ws.p_actor_t, anet.l[1],
                             ws.at_h2, ACT_NONE),
                     fwd_job(ws.c_h1, ws.ba, ws.p_critic, cnet.l[1], ws.c_h2,
-                            ACT_RELU)});
+                            ACT_RELU)}, bf);
         // P4: a_t.L3 | c.L3
         launch_fwd({fwd_job(ws.at_h2, nullptr, ws.p_actor_t, anet.l[2],
                             ws.at_h3, ACT_RELU),
                     fwd_job(ws.c_h2, nullptr, ws.p_critic, cnet.l[2], ws.c_h3,
-                            ACT_RELU)});
+                            ACT_RELU)}, bf);
         // P5: a_t.L4 tanh | c.L4 softmax -> q
         launch_fwd({fwd_job(ws.at_h3, nullptr, ws.p_actor_t, anet.l[3], ws.a2,
                             ACT_TANH),
                     fwd_job(ws.c_h3, nullptr, ws.p_critic, cnet.l[3], ws.q,
-                            ACT_SOFTMAX)});
+                            ACT_SOFTMAX)}, bf);
         // P6-8: c_t.L2(cat ct_h1, a2), c_t.L3, c_t.L4 softmax -> p_t
         launch_fwd({fwd_job(ws.ct_h1, ws.a2, ws.p_critic_t, cnet.l[1], ws.ct_h2,
-                            ACT_RELU)});
+                            ACT_RELU)}, bf);
         launch_fwd({fwd_job(ws.ct_h2, nullptr, ws.p_critic_t, cnet.l[2],
-                            ws.ct_h3, ACT_RELU)});
+                            ws.ct_h3, ACT_RELU)}, bf);
         launch_fwd({fwd_job(ws.ct_h3, nullptr, ws.p_critic_t, cnet.l[3], ws.p_t,
-                            ACT_SOFTMAX)});
+                            ACT_SOFTMAX)}, bf);
         // P9+P10 fused: projection + CE grad + priorities
         hipLaunchKernelGGL(k_project_ce, dim3(min(row_wgs, 256)),
                            dim3(256),
@@ -598,13 +619,13 @@ public:
                            cfg.per_eps, cfg.is_weighting, cfg.true_td);
         // P11-14: critic backward L4..L1
         launch_bwd(ws.dlog, ws.c_h3, nullptr, ws.p_critic, ws.g_critic,
-                   cnet.l[3], ws.d3, nullptr, ws.c_h3, ACT_RELU, true);
+                   cnet.l[3], ws.d3, nullptr, ws.c_h3, ACT_RELU, true, bf);
         launch_bwd(ws.d3, ws.c_h2, nullptr, ws.p_critic, ws.g_critic, cnet.l[2],
-                   ws.d2, nullptr, ws.c_h2, ACT_RELU, true);
+                   ws.d2, nullptr, ws.c_h2, ACT_RELU, true, bf);
         launch_bwd(ws.d2, ws.c_h1, ws.ba, ws.p_critic, ws.g_critic, cnet.l[1],
-                   ws.d1, nullptr, ws.c_h1, ACT_RELU, true);
+                   ws.d1, nullptr, ws.c_h1, ACT_RELU, true, bf);
         launch_bwd(ws.d1, ws.bs, nullptr, ws.p_critic, ws.g_critic, cnet.l[0],
-                   nullptr, nullptr, nullptr, ACT_NONE, true);
+                   nullptr, nullptr, nullptr, ACT_NONE, true, bf);
         }
         // P15: Adam critic + target soft-update fused
         if (mask & PH_CRITIC_APPLY) launch_adam_lerp(false);
@@ -613,45 +634,47 @@ public:
         launch_fwd({fwd_job(ws.bs, nullptr, ws.p_actor, anet.l[0], ws.pa_h1,
                             ACT_RELU),
                     fwd_job(ws.bs, nullptr, ws.p_critic, cnet.l[0], ws.pc_h1,
-                            ACT_RELU)});
+                            ACT_RELU)}, bf);
         // P17-19: actor L2, L3, L4
         launch_fwd({fwd_job(ws.pa_h1, nullptr, ws.p_actor, anet.l[1], ws.pa_h2,
-                            ACT_NONE)});
+                            ACT_NONE)}, bf);
         launch_fwd({fwd_job(ws.pa_h2, nullptr, ws.p_actor, anet.l[2], ws.pa_h3,
-                            ACT_RELU)});
+                            ACT_RELU)}, bf);
         launch_fwd({fwd_job(ws.pa_h3, nullptr, ws.p_actor, anet.l[3], ws.a_out,
-                            ACT_TANH)});
+                            ACT_TANH)}, bf);
         // P20-22: critic'(s, a_out)
         launch_fwd({fwd_job(ws.pc_h1, ws.a_out, ws.p_critic, cnet.l[1],
-                            ws.pc_h2, ACT_RELU)});
+                            ws.pc_h2, ACT_RELU)}, bf);
         launch_fwd({fwd_job(ws.pc_h2, nullptr, ws.p_critic, cnet.l[2], ws.pc_h3,
-                            ACT_RELU)});
+                            ACT_RELU)}, bf);
         launch_fwd({fwd_job(ws.pc_h3, nullptr, ws.p_critic, cnet.l[3], ws.pq,
-                            ACT_SOFTMAX)});
+                            ACT_SOFTMAX)}, bf);
         // P23: policy head gradient
         hipLaunchKernelGGL(k_policy_grad, dim3(min(row_wgs, 256)),
                            dim3(256), 0, stream,
                            ws.pq, ws.pd3, ws.cnt, B, K, cfg.v_min, cfg.v_max);
         // P24-26: dX back through critic' (no dW), ending at da
         launch_bwd(ws.pd3, ws.pc_h3, nullptr, ws.p_critic, nullptr, cnet.l[3],
-                   ws.pd2, nullptr, ws.pc_h3, ACT_RELU, false);
+                   ws.pd2, nullptr, ws.pc_h3, ACT_RELU, false, bf);
         launch_bwd(ws.pd2, ws.pc_h2, nullptr, ws.p_critic, nullptr, cnet.l[2],
-                   ws.pdh1, nullptr, ws.pc_h2, ACT_RELU, false);
+                   ws.pdh1, nullptr, ws.pc_h2, ACT_RELU, false, bf);
         launch_bwd(ws.pdh1, ws.pc_h1, ws.a_out, ws.p_critic, nullptr, cnet.l[1],
-                   nullptr, ws.pda, ws.pc_h1, ACT_RELU, false);
+                   nullptr, ws.pda, ws.pc_h1, ACT_RELU, false, bf);
         // P27: tanh backward at actor output
         hipLaunchKernelGGL(k_tanh_bwd, dim3(ceil_div((long)B * cfg.act, 256)),
                            dim3(256), 0, stream, ws.pda, ws.a_out, ws.adz,
                            (long)B * cfg.act);
-        // P28-31: actor backward L4..L1 (with dW)
+        // P28-31: actor backward L4..L1 (with dW).  az3/az2/az1 are the
+        // deltas at the actor's layers 3/2/1, the names they carry on the
+        // row-block path: every GEMM's dz outlives the phase (read_buffer)
         launch_bwd(ws.adz, ws.pa_h3, nullptr, ws.p_actor, ws.g_actor, anet.l[3],
-                   ws.pd2 /*reuse*/, nullptr, ws.pa_h3, ACT_RELU, true);
-        launch_bwd(ws.pd2, ws.pa_h2, nullptr, ws.p_actor, ws.g_actor, anet.l[2],
-                   ws.pdh1, nullptr, ws.pa_h2, ACT_NONE, true);
-        launch_bwd(ws.pdh1, ws.pa_h1, nullptr, ws.p_actor, ws.g_actor,
-                   anet.l[1], ws.pd2, nullptr, ws.pa_h1, ACT_RELU, true);
-        launch_bwd(ws.pd2, ws.bs, nullptr, ws.p_actor, ws.g_actor, anet.l[0],
-                   nullptr, nullptr, nullptr, ACT_NONE, true);
+                   ws.az3, nullptr, ws.pa_h3, ACT_RELU, true, bf);
+        launch_bwd(ws.az3, ws.pa_h2, nullptr, ws.p_actor, ws.g_actor, anet.l[2],
+                   ws.az2, nullptr, ws.pa_h2, ACT_NONE, true, bf);
+        launch_bwd(ws.az2, ws.pa_h1, nullptr, ws.p_actor, ws.g_actor,
+                   anet.l[1], ws.az1, nullptr, ws.pa_h1, ACT_RELU, true, bf);
+        launch_bwd(ws.az1, ws.bs, nullptr, ws.p_actor, ws.g_actor, anet.l[0],
+                   nullptr, nullptr, nullptr, ACT_NONE, true, bf);
         }
         if (!(mask & PH_ACTOR_APPLY)) return;
         // P32: Adam actor + target soft-update fused (critic target was

@@ -82,6 +82,8 @@ struct EngineCfg {
     int is_weighting;          // apply IS weights to the CE loss
     int prioritized = 1;       // 0: uniform replay, no sum/min trees
     int true_td = 0;           // priority |E_m[z] - E_q[z]| for <m, q>
+    int gemm_bf16 = 0;         // wide train step: bf16 MFMA operands (RNE),
+                               // fp32 accumulate; batch > 512 only
 };
 
 // device-side counters (one small block)
@@ -166,7 +168,9 @@ struct StepArgs {
     float *c_h1, *c_h2, *c_h3, *q, *dlog, *d3, *d2, *d1;   // critic + deltas
     float *pa_h1, *pa_h2, *pa_h3, *a_out;           // actor (policy) path
     float *pc_h1, *pc_h2, *pc_h3, *pq;              // critic(s, actor(s))
-    float *pd3, *pd2, *pdh1, *adz, *az1, *az2, *az3;    // policy deltas
+    // policy deltas (az1..3: at the actor's layers 1..3, both the row-block
+    // and the wide path)
+    float *pd3, *pd2, *pdh1, *adz, *az1, *az2, *az3;
     Counters* cnt;
     unsigned long long* gbar;        // persistent grid barrier state
     unsigned long long* tstamp;      // [64] per-phase s_memrealtime stamps

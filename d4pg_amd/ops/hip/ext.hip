@@ -26,7 +26,7 @@ static int64_t create(int64_t obs, int64_t act, int64_t hidden, int64_t atoms,
                       double lr_actor, double lr_critic, double per_alpha,
                       double per_beta0, int64_t per_beta_iters,
                       double per_eps, int64_t seed, bool is_weighting,
-                      bool prioritized, bool true_td) {
+                      bool prioritized, bool true_td, bool gemm_bf16) {
     EngineCfg c{};
     c.obs = (int)obs; c.act = (int)act; c.hidden = (int)hidden;
     c.atoms = (int)atoms; c.batch = (int)batch;
@@ -38,6 +38,7 @@ static int64_t create(int64_t obs, int64_t act, int64_t hidden, int64_t atoms,
     c.per_beta_iters = per_beta_iters; c.per_eps = (float)per_eps;
     c.seed = (uint64_t)seed; c.is_weighting = is_weighting ? 1 : 0;
     c.prioritized = prioritized ? 1 : 0; c.true_td = true_td ? 1 : 0;
+    c.gemm_bf16 = gemm_bf16 ? 1 : 0;
     int64_t h = g_next++;
     g_engines[h] = std::make_unique<Engine>(c);
     return h;
@@ -53,6 +54,7 @@ static py::dict info(int64_t h) {
     d["tree_cap"] = e.ws.tree_cap;      // 0 on uniform replay (no trees)
     d["prioritized"] = e.cfg.prioritized != 0;
     d["true_td"] = e.cfg.true_td != 0;
+    d["gemm_precision"] = e.cfg.gemm_bf16 ? "bf16" : "fp32";
     d["persistent"] = e.step_path() == Engine::PATH_PERSISTENT;
     d["seed"] = (int64_t)e.cfg.seed;
     py::list al, cl;
@@ -587,6 +589,30 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
         {"c_h2", {e.ws.c_h2, {B, H}, false, false}},
         {"c_h3", {e.ws.c_h3, {B, H}, false, false}},
         {"at_h1", {e.ws.at_h1, {B, H}, false, false}},
+        // the wide step's remaining GEMM inputs and outputs (per-GEMM
+        // tests, tests/test_gpu_wide_bf16.py)
+        {"at_h2", {e.ws.at_h2, {B, H}, false, false}},
+        {"at_h3", {e.ws.at_h3, {B, H}, false, false}},
+        {"ct_h1", {e.ws.ct_h1, {B, H}, false, false}},
+        {"ct_h2", {e.ws.ct_h2, {B, H}, false, false}},
+        {"ct_h3", {e.ws.ct_h3, {B, H}, false, false}},
+        {"d1", {e.ws.d1, {B, H}, false, false}},
+        {"d2", {e.ws.d2, {B, H}, false, false}},
+        {"d3", {e.ws.d3, {B, H}, false, false}},
+        {"pa_h1", {e.ws.pa_h1, {B, H}, false, false}},
+        {"pa_h2", {e.ws.pa_h2, {B, H}, false, false}},
+        {"pa_h3", {e.ws.pa_h3, {B, H}, false, false}},
+        {"pc_h1", {e.ws.pc_h1, {B, H}, false, false}},
+        {"pc_h2", {e.ws.pc_h2, {B, H}, false, false}},
+        {"pc_h3", {e.ws.pc_h3, {B, H}, false, false}},
+        {"pd3", {e.ws.pd3, {B, K}, false, false}},
+        {"pd2", {e.ws.pd2, {B, H}, false, false}},
+        {"pdh1", {e.ws.pdh1, {B, H}, false, false}},
+        {"pda", {e.ws.pda, {B, A}, false, false}},
+        {"adz", {e.ws.adz, {B, A}, false, false}},
+        {"az1", {e.ws.az1, {B, H}, false, false}},
+        {"az2", {e.ws.az2, {B, H}, false, false}},
+        {"az3", {e.ws.az3, {B, H}, false, false}},
         {"tstamp", {e.ws.tstamp, {64}, true, false}},
         {"sum_tree", {e.ws.sum_tree, {2 * e.ws.tree_cap}, false, true}},
         {"min_tree", {e.ws.min_tree, {2 * e.ws.tree_cap}, false, true}},
@@ -620,7 +646,17 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
 }  // namespace d4pg
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
-    mod.def("create", &d4pg::create);
+    // gemm_bf16 is the one trailing argument with a default
+    mod.def("create", &d4pg::create,
+            py::arg("obs"), py::arg("act"), py::arg("hidden"),
+            py::arg("atoms"), py::arg("batch"), py::arg("capacity"),
+            py::arg("v_min"), py::arg("v_max"), py::arg("gamma_n"),
+            py::arg("tau"), py::arg("lr_actor"), py::arg("lr_critic"),
+            py::arg("per_alpha"), py::arg("per_beta0"),
+            py::arg("per_beta_iters"), py::arg("per_eps"), py::arg("seed"),
+            py::arg("is_weighting"), py::arg("prioritized"),
+            py::arg("true_td"),
+            py::arg("gemm_bf16") = false);
     mod.def("destroy", &d4pg::destroy);
     mod.def("info", &d4pg::info);
     mod.def("load_slab", &d4pg::load_slab);

@@ -31,7 +31,9 @@ def _build_agent(args, env, seed):
                 batch_size=args.bsize, gamma=args.gamma, tau=args.tau,
                 prioritized_replay=bool(args.p_replay),
                 critic_dist_info=critic_dist_info(args),
-                n_steps=args.n_steps, seed=seed, **noise_kwargs(args))
+                n_steps=args.n_steps, seed=seed,
+                gemm_precision=getattr(args, "gemm_precision", "fp32"),
+                **noise_kwargs(args))
 
 
 def _worker_main(name, args, global_model, global_count, opt_actor,

@@ -170,7 +170,11 @@ class DistributedD4PG:
             prioritized_replay=bool(args.p_replay) and self.is_learner,
             critic_dist_info=critic_dist_info(args), n_steps=args.n_steps,
             device=str(self.device) if self.is_learner else "cpu",
-            backend=backend, seed=seed, **noise_kwargs(args))
+            backend=backend, seed=seed,
+            # a learner-side option: actor and evaluator ranks only act
+            gemm_precision=(getattr(args, "gemm_precision", "fp32")
+                            if self.is_learner else "fp32"),
+            **noise_kwargs(args))
         self.rng = np.random.default_rng(seed)
 
         # wire geometry: per-round per-rank transition cap.  HER can add up

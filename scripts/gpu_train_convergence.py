@@ -4,6 +4,7 @@ product path (Worker + fused HIP engine) and report eval returns per cycle.
 Random policy scores ~-1200..-1500; a learning agent reaches -150..-400.
 
 Usage: python scripts/gpu_train_convergence.py [cycles] [--vector_envs M]
+           [--bsize B] [--gemm_precision {fp32,bf16}]
 
 With --vector_envs M > 0 (and a GPU) the Worker takes the closed on-GPU
 cycle: M-env device episodes collect into the learner's replay and the
@@ -28,16 +29,19 @@ import argparse  # noqa: E402
 _cli = argparse.ArgumentParser()
 _cli.add_argument("cycles", nargs="?", type=int, default=30)
 _cli.add_argument("--vector_envs", type=int, default=0)
+_cli.add_argument("--bsize", type=int, default=64)
+_cli.add_argument("--gemm_precision", default="fp32", choices=["fp32", "bf16"])
 _opts = _cli.parse_args()
 cycles = _opts.cycles
 
 args = make_parser().parse_args(
     ["--env", "Pendulum-v1", "--max_steps", "200", "--warmup", "5",
-     "--rmsize", "1000000", "--bsize", "64", "--n_steps", "5",
+     "--rmsize", "1000000", "--bsize", str(_opts.bsize), "--n_steps", "5",
      "--n_eps", "1000", "--cycles_per_epoch", "1000000", "--debug", "0",
      "--episodes_per_cycle", "8", "--train_steps_per_cycle", "600",
      "--eval_trials", "3", "--seed", "0",
-     "--vector_envs", str(_opts.vector_envs)])
+     "--vector_envs", str(_opts.vector_envs),
+     "--gemm_precision", _opts.gemm_precision])
 configure_env_params(args)
 
 env = make(args.env, seed=0)
@@ -51,7 +55,8 @@ agent = DDPG(obs_dim, act_dim, env=env, memory_size=args.rmsize,
              critic_dist_info={"type": "categorical", "v_min": -300.0,
                                "v_max": 0.0, "n_atoms": 51},
              n_steps=args.n_steps, lr_actor=1e-4, lr_critic=1e-3,
-             device=device, backend=backend, seed=0)
+             device=device, backend=backend, seed=0,
+             gemm_precision=args.gemm_precision)
 w = Worker("conv", args, agent, env, run_dir="")
 w.warmup()
 t0 = time.perf_counter()

@@ -48,7 +48,8 @@ def main(argv=None):
                  prioritized_replay=bool(args.p_replay),
                  critic_dist_info=critic_dist_info(args),
                  n_steps=args.n_steps, device=device, backend=backend,
-                 seed=args.seed, **noise_kwargs(args))
+                 seed=args.seed, gemm_precision=args.gemm_precision,
+                 **noise_kwargs(args))
     rd = run_dir_name(args)
     writer = SummaryWriter(rd)
     worker = Worker("1", args, agent, env, writer=writer, run_dir=rd)
