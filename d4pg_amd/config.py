@@ -116,6 +116,16 @@ def make_parser() -> argparse.ArgumentParser:
                         "(env dynamics + policy + noise + n-step fold as "
                         "HIP kernels): 1 = force, 0 = off, -1 = auto "
                         "(on when the rank sees a GPU)")
+    p.add_argument("--async_collect", default=0, type=int, choices=[0, 1],
+                   help="1: overlap device collection with training on one "
+                        "GPU.  After a serial warmup each cycle opens a "
+                        "collection window on a second HIP stream, trains, "
+                        "then commits the window's rows, so rows collected "
+                        "with the policy of cycle k are sampled from cycle "
+                        "k+1 on.  Needs the device collect path (backend "
+                        "hip, --vector_envs M > 0, --gpu_actors != 0 and "
+                        "an env a device rollout models); refused "
+                        "otherwise.  0: collect, then train (default)")
     p.add_argument("--gemm_precision", default="fp32", type=str,
                    choices=list(GEMM_PRECISIONS),
                    help="MFMA operand type of the hip backend's wide train "
@@ -221,6 +231,7 @@ class D4PGConfig:
     gpu_actors: int = -1
     her_ratio: float = 0.8
     gemm_precision: str = "fp32"
+    async_collect: int = 0
     extra: dict = field(default_factory=dict)
 
     @classmethod

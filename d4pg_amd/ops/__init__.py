@@ -426,6 +426,32 @@ class FusedEngine:
     def synth_rollout_info(self):
         return self.ext.synth_rollout_info(self.h)
 
+    # -- overlapped collection (ops/hip/engine_stage.hip): the allocated
+    # producer's episodes on a second stream while this engine trains; rows
+    # reach the replay at the commit (ARCHITECTURE.md, "Overlapped
+    # collection") --
+    def collect_alloc(self, max_episodes):
+        """Allocate the staging store for windows of up to `max_episodes`
+        device episodes (call after a *_rollout_alloc; a new one frees it)."""
+        self.ext.collect_alloc(self.h, int(max_episodes))
+
+    def collect_begin(self, episodes=1, use_graph=True):
+        """Open a collection window: snapshot the actor, enqueue `episodes`
+        episodes on the rollout stream and return at once.  step /
+        train_steps / step_part / evaluate / ingest and the read accessors
+        stay legal until collect_commit(); the sync rollout calls, the
+        rollout allocators, set_seed and the replay save/load refuse."""
+        self.ext.collect_begin(self.h, int(episodes), bool(use_graph))
+
+    def collect_commit(self):
+        """Close the window: copy its rows into the live ring on the
+        learner stream (after every step issued so far), wait, and return
+        (env_steps, rows) of the window."""
+        return tuple(self.ext.collect_commit(self.h))
+
+    def collect_pending(self):
+        return bool(self.ext.collect_pending(self.h))
+
     # -- device greedy evaluation (ops/hip/engine_eval.hip): noise-free
     # episodes of the allocated rollout producer's env, in a pool of their
     # own; nothing training reads is written --
@@ -489,7 +515,8 @@ class FusedEngine:
     def rollout_last_rows(self):
         """Host copy of the rows of the LAST rollout episode only, in write
         order, from its replay base and row count (replay_rows() returns
-        every occupied slot)."""
+        every occupied slot).  After a collect_commit(): the committed
+        block, from its live base."""
         base, count = self.ext.rollout_last(self.h)
         s, a, r, s2, d = self.ext.replay_slice(self.h, int(base), int(count))
         return (s.numpy(), a.numpy(), r.numpy().ravel(), s2.numpy(),

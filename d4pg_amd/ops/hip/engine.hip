@@ -23,6 +23,8 @@
 // device pool layout, the launch sequences of the three paths, hipGraph
 // capture and replay, replay ingestion, parameter I/O, the rollout driver.
 
+#include <string>
+
 #include "engine_common.hip"
 #include "engine_rowmath.hip"
 #include "engine_replay.hip"
@@ -33,6 +35,7 @@
 #include "engine_goal.hip"
 #include "engine_synth.hip"
 #include "engine_eval.hip"
+#include "engine_stage.hip"
 #include "engine_mfma.hip"
 #include "engine_mfma_bf16.hip"
 #include "engine_persistent.hip"
@@ -147,9 +150,19 @@ public:
     // level (bulk ingest, synth_fill, once per rollout episode)
     void launch_tree_rebuild(int wgs) {
         if (!has_trees()) return;
-        for (long lo = ws.tree_cap / 2; lo >= 1; lo >>= 1)
+        launch_tree_rebuild(wgs, stream, ws.sum_tree, ws.min_tree,
+                            ws.tree_cap);
+    }
+
+    // the same sweep on the caller's stream over the caller's trees; null
+    // trees (uniform replay, or a rollout core pointed at the staging store
+    // of an overlapped collection) make it a no-op
+    void launch_tree_rebuild(int wgs, hipStream_t st, double* sum_tree,
+                             double* min_tree, long tree_cap) {
+        if (!sum_tree) return;
+        for (long lo = tree_cap / 2; lo >= 1; lo >>= 1)
             hipLaunchKernelGGL(k_tree_build_level, dim3(wgs), dim3(256), 0,
-                               stream, ws.sum_tree, ws.min_tree, lo, 2 * lo);
+                               st, sum_tree, min_tree, lo, 2 * lo);
     }
 
     // the persistent grid barrier's timeout flag (gbar[176]); raised on
@@ -166,7 +179,14 @@ public:
     }
 
     ~Engine() {
+        // drain the rollout stream first: an open window's episodes read
+        // and write the pools freed below
+        if (roll_stream_) hipStreamSynchronize(roll_stream_);
+        collect_pending_ = false;
         rollout_free();
+        if (ev_snap_) hipEventDestroy(ev_snap_);
+        if (ev_done_) hipEventDestroy(ev_done_);
+        if (roll_stream_) hipStreamDestroy(roll_stream_);
         if (graph_exec) hipGraphExecDestroy(graph_exec);
         if (graph) hipGraphDestroy(graph);
         hipStreamDestroy(stream);
@@ -343,19 +363,25 @@ public:
     // (the train step has its own split, see step_path()).
     static bool fwd_uses_mfma(int rows) { return rows >= 512; }
 
-    void launch_fwd_valu(const FwdJob& j) {
+    // (the launchers the rollout uses take their stream; the train step's
+    // run on the engine's)
+    void launch_fwd_valu(const FwdJob& j, hipStream_t st) {
         hipLaunchKernelGGL(k_fwd, dim3(j.nwg_b * j.nwg_o), dim3(256), 0,
-                           stream, j);
+                           st, j);
     }
+    void launch_fwd_valu(const FwdJob& j) { launch_fwd_valu(j, stream); }
 
     // bf16 (here and below): the bf16-operand twin of the kernel, same grid
     // and arguments — only the wide train step in gemm_bf16 mode passes it.
-    void launch_fwd_mfma(const FwdJob& j, bool bf16 = false) {
+    void launch_fwd_mfma(const FwdJob& j, bool bf16, hipStream_t st) {
         int ntm = ceil_div(j.B, MT_M), ntn = ceil_div(j.out, MT_N);
         hipLaunchKernelGGL(bf16 ? k_mfma_fwd_bf16 : k_mfma_fwd,
-                           dim3(ntm * ntn), dim3(256), 0, stream,
+                           dim3(ntm * ntn), dim3(256), 0, st,
                            j.x1, j.x2, j.wt, j.bias, j.y, j.B, j.in1, j.in2,
                            j.out, j.act, 1, (float*)nullptr);
+    }
+    void launch_fwd_mfma(const FwdJob& j, bool bf16 = false) {
+        launch_fwd_mfma(j, bf16, stream);
     }
 
     // Narrow head (out <= 64, incl. the softmax ones): split-K partials in
@@ -880,17 +906,31 @@ public:
     enum { ROLL_NONE = 0, ROLL_PENDULUM = 1, ROLL_GOAL = 2, ROLL_SYNTH = 3 };
     int roll_kind_ = ROLL_NONE;
 
-    RollCore& roll_core() {
-        if (roll_kind_ == ROLL_GOAL) return goal_;
-        if (roll_kind_ == ROLL_SYNTH) return syn_;
-        return roll_;
+    // staged: the producer's args pointed at the staging store of an
+    // overlapped collection (collect_alloc below)
+    RollCore& roll_core(bool staged = false) {
+        if (roll_kind_ == ROLL_GOAL) return staged ? goal_st_ : goal_;
+        if (roll_kind_ == ROLL_SYNTH) return staged ? syn_st_ : syn_;
+        return staged ? roll_st_ : roll_;
     }
 
     void roll_require(int kind, const char* otherwise) {
         if (roll_kind_ != kind) throw std::runtime_error(otherwise);
     }
 
+    // Everything that reads or moves what an open collection window is
+    // using (the producer's env state and words, its pools, the seeds, a
+    // host copy of the whole replay) waits for the commit.
+    void refuse_in_window(const char* what) {
+        if (collect_pending_)
+            throw std::runtime_error(
+                std::string(what) + ": a collection window is open "
+                "(collect_begin ran); call collect_commit first");
+    }
+
     void rollout_free() {
+        refuse_in_window("rollout_free / *_rollout_alloc");
+        collect_free();                 // the staging store of this producer
         eval_free();                    // the evaluation models this producer
         if (roll_graph_exec) { hipGraphExecDestroy(roll_graph_exec);
                                roll_graph_exec = nullptr; }
@@ -951,20 +991,24 @@ public:
     }
 
     // the policy forward obs [M][obs] -> act [M][act] between two ticks
-    void roll_fwd_chain(const float* obs, float* act, int M) {
-        roll_fwd_chain(obs, act, M, r_h1, r_h2, r_h3);
+    // on stream st with the weights of `slab`: the engine's stream and
+    // ws.p_actor, or the rollout stream and the snapshot p_actor_roll
+    void roll_fwd_chain(const float* obs, float* act, int M, hipStream_t st,
+                        const float* slab) {
+        roll_fwd_chain(obs, act, M, r_h1, r_h2, r_h3, st, slab);
     }
 
     // the same chain over hidden buffers [M][hidden] of the caller's
     void roll_fwd_chain(const float* obs, float* act, int M, float* h1,
-                        float* h2, float* h3) {
+                        float* h2, float* h3, hipStream_t st,
+                        const float* slab) {
         // (the tanh head takes the plain MFMA launch here, not the split-K
         // head pair: dw_parts is sized for the learner batch, not for M)
         auto run = [&](const float* x, const LayerDesc& l, float* y,
                        int actk) {
-            FwdJob j = fwd_job(x, nullptr, ws.p_actor, l, y, actk, M);
-            if (fwd_uses_mfma(M)) launch_fwd_mfma(j);
-            else launch_fwd_valu(j);
+            FwdJob j = fwd_job(x, nullptr, slab, l, y, actk, M);
+            if (fwd_uses_mfma(M)) launch_fwd_mfma(j, false, st);
+            else launch_fwd_valu(j, st);
         };
         run(obs, anet.l[0], h1, ACT_RELU);
         run(h1, anet.l[1], h2, ACT_NONE);       // fc2->fc2_2 no-act quirk
@@ -972,17 +1016,25 @@ public:
         run(h3, anet.l[3], act, ACT_TANH);
     }
 
-    // one whole episode of the allocated producer, on the engine's stream
-    void enqueue_episode(bool reset) {
-        hipLaunchKernelGGL(k_roll_begin, dim3(1), dim3(64), 0, stream,
-                           roll_core());
-        if (roll_kind_ == ROLL_GOAL) goal_enqueue_ticks(reset);
-        else if (roll_kind_ == ROLL_SYNTH) synth_enqueue_ticks(reset);
-        else pendulum_enqueue_ticks(reset);
+    // one whole episode of the allocated producer: on the engine's stream
+    // into the live replay with the live actor, or (staged) on the rollout
+    // stream into the staging store with the snapshot actor
+    void enqueue_episode(bool reset, bool staged = false) {
+        hipStream_t st = staged ? roll_stream_ : stream;
+        const float* slab = staged ? p_actor_roll : ws.p_actor;
+        RollCore& c = roll_core(staged);
+        hipLaunchKernelGGL(k_roll_begin, dim3(1), dim3(64), 0, st, c);
+        if (roll_kind_ == ROLL_GOAL)
+            goal_enqueue_ticks(staged ? goal_st_ : goal_, reset, st, slab);
+        else if (roll_kind_ == ROLL_SYNTH)
+            synth_enqueue_ticks(staged ? syn_st_ : syn_, reset, st, slab);
+        else
+            pendulum_enqueue_ticks(staged ? roll_st_ : roll_, reset, st,
+                                   slab);
         // internal tree nodes: one bandwidth-bound full sweep per episode
         // (vs horizon x per-path repair) — leaves were set at emit; a no-op
-        // on uniform replay
-        launch_tree_rebuild(1024);
+        // where the core has no trees (uniform replay, the staging store)
+        launch_tree_rebuild(1024, st, c.sum_tree, c.min_tree, c.tree_cap);
     }
 
     // `episodes` whole episodes and the synchronise after them; with
@@ -1016,6 +1068,226 @@ public:
                             hipMemcpyDeviceToHost));
     }
 
+    // ---------------- overlapped collection (engine_stage.hip) -----------
+    // collect_begin .. collect_commit is one collection WINDOW: the
+    // allocated producer's episodes run on a second stream while the
+    // learner stream trains, and their rows reach the replay at the commit.
+    //
+    // Staging, not concurrent ring writes.  The window's episodes run the
+    // unchanged episode kernels over a copy of the producer's args whose
+    // replay fields point at a staging store (no trees, its own Counters,
+    // capacity = max_episodes x rows-per-episode), and read the policy from
+    // p_actor_roll, a snapshot of p_actor taken on the learner stream at
+    // collect_begin.  Nothing the train step reads is written before the
+    // commit, and nothing the episodes read is written by the train step.
+    // Env state, n-step rings, the hidden buffers r_h1..3 and the philox
+    // epoch (ep_state[0]) are the producer's own and are shared with the
+    // sync path, which is refused while a window is open: episodes continue
+    // one epoch sequence across sync and staged runs alike.
+    //
+    // Ordering is by two events and nothing else.  ev_snap_: recorded on
+    // the learner stream after the snapshot copy, waited on by the rollout
+    // stream before the first episode (it also orders the episodes after
+    // any earlier sync rollout, which ran on the learner stream).  ev_done_:
+    // recorded on the rollout stream after the last episode, waited on by
+    // the learner stream before k_stage_commit.  The host synchronises only
+    // at the end of collect_commit.
+    //
+    // Co-residency of the persistent step.  k_step_persistent's software
+    // grid barrier needs its PNWG workgroups resident at once.  Rollout
+    // kernels can hold CU slots while it starts, but they wait on nothing
+    // the learner produces: their one dependency, ev_snap_, was recorded
+    // BEFORE any train launch of the window.  So every rollout kernel runs
+    // to completion and frees its slots whatever the learner does, and the
+    // persistent grid always becomes resident.  The reverse wait (the
+    // commit on ev_done_) sits on the learner stream behind the train
+    // launches, not inside one.  Never make the rollout stream wait on
+    // learner work issued after collect_begin: that would close a cycle
+    // through the barrier.  The episode graph stays a single-stream graph
+    // (no cross-stream fork or join is captured); the staged path has its
+    // own, because its kernel arguments differ.
+    RollArgs roll_st_{};
+    GoalRollArgs goal_st_{};
+    SynRollArgs syn_st_{};
+    void* stage_pool_ = nullptr;
+    float *st_rs = nullptr, *st_ra = nullptr, *st_rr = nullptr,
+          *st_rs2 = nullptr, *st_rd = nullptr;
+    Counters* st_cnt = nullptr;
+    float* p_actor_roll = nullptr;
+    long stage_rows_ = 0;               // staging capacity in rows
+    int collect_max_episodes_ = 0;
+    int collect_episodes_ = 0;          // of the open window
+    bool collect_pending_ = false;
+    hipStream_t roll_stream_ = nullptr;
+    hipEvent_t ev_snap_ = nullptr, ev_done_ = nullptr;
+    hipGraph_t stage_graph = nullptr;
+    hipGraphExec_t stage_graph_exec = nullptr;
+
+    void collect_free() {
+        if (stage_graph_exec) { hipGraphExecDestroy(stage_graph_exec);
+                                stage_graph_exec = nullptr; }
+        if (stage_graph) { hipGraphDestroy(stage_graph);
+                           stage_graph = nullptr; }
+        if (stage_pool_) { hipFree(stage_pool_); stage_pool_ = nullptr; }
+        collect_max_episodes_ = 0;
+        stage_rows_ = 0;
+    }
+
+    // rows one episode of the allocated producer writes at most
+    long roll_episode_rows() {
+        const RollCore& c = roll_core();
+        if (roll_kind_ == ROLL_GOAL)
+            return goal_episode_max(c.M, c.n, c.horizon);
+        return (long)c.M * (c.horizon - c.n + 1);
+    }
+
+    void collect_alloc(int max_episodes) {
+        refuse_in_window("collect_alloc");
+        if (roll_kind_ == ROLL_NONE)
+            throw std::runtime_error(
+                "collect_alloc: no rollout allocated (call it after a "
+                "*_rollout_alloc)");
+        if (max_episodes < 1)
+            throw std::runtime_error("collect_alloc: max_episodes < 1");
+        const long rows = (long)max_episodes * roll_episode_rows();
+        if (rows > cfg.capacity)
+            throw std::runtime_error(
+                "collect_alloc: max_episodes windows of " +
+                std::to_string(rows) + " staged rows exceed the replay "
+                "capacity " + std::to_string(cfg.capacity) + " (one commit "
+                "would map two rows to one slot)");
+        collect_free();
+        if (!roll_stream_) {
+            // below the learner stream where the runtime has priorities
+            // (numerically larger = lower); the range is [0, 0] where not
+            int least = 0, greatest = 0;
+            HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            HIP_CHECK(hipStreamCreateWithPriority(
+                &roll_stream_, hipStreamNonBlocking, least));
+            HIP_CHECK(hipEventCreateWithFlags(&ev_snap_,
+                                              hipEventDisableTiming));
+            HIP_CHECK(hipEventCreateWithFlags(&ev_done_,
+                                              hipEventDisableTiming));
+        }
+        const long O = cfg.obs, A = cfg.act;
+        char* base = nullptr;
+        long off = 0;
+        auto sub = [&](auto*& p, long nelem) {      // nelem in 4-byte words
+            if (base) p = reinterpret_cast<decltype(+p)>(base + off);
+            off += (nelem * 4 + 255) & ~255L;
+        };
+        auto carve_all = [&] {
+            off = 0;
+            sub(st_rs, rows * O); sub(st_ra, rows * A); sub(st_rr, rows);
+            sub(st_rs2, rows * O); sub(st_rd, rows);
+            sub(st_cnt, (long)(sizeof(Counters) + 3) / 4);
+            sub(p_actor_roll, anet.n_params);
+        };
+        carve_all();
+        HIP_CHECK(hipMalloc(&stage_pool_, off));
+        HIP_CHECK(hipMemset(stage_pool_, 0, off));
+        base = (char*)stage_pool_;
+        carve_all();
+        HIP_CHECK(hipDeviceSynchronize());
+        // the producer's args over the staging store: with null trees
+        // roll_leaf_value / roll_write_leaf are no-ops, and k_roll_begin,
+        // k_roll_end, k_goal_end and roll_advance work on the staging words
+        roll_st_ = roll_; goal_st_ = goal_; syn_st_ = syn_;
+        RollCore& c = roll_core(true);
+        c.rs = st_rs; c.ra = st_ra; c.rr = st_rr; c.rs2 = st_rs2;
+        c.rd = st_rd;
+        c.sum_tree = c.min_tree = nullptr;
+        c.tree_cap = 0;
+        c.capacity = rows;
+        c.cnt = st_cnt;
+        stage_rows_ = rows;
+        collect_max_episodes_ = max_episodes;
+    }
+
+    // snapshot the actor, enqueue `episodes` staged episodes on the rollout
+    // stream and return without waiting for any of it
+    void collect_begin(int episodes, bool use_graph) {
+        if (!stage_pool_)
+            throw std::runtime_error("collect_begin: collect_alloc first");
+        if (collect_pending_)
+            throw std::runtime_error(
+                "collect_begin: a collection window is already open; call "
+                "collect_commit first");
+        if (episodes < 1 || episodes > collect_max_episodes_)
+            throw std::runtime_error(
+                "collect_begin: episodes not in [1, max_episodes = " +
+                std::to_string(collect_max_episodes_) + "]");
+        HIP_CHECK(hipMemcpyAsync(p_actor_roll, ws.p_actor,
+                                 anet.n_params * 4, hipMemcpyDeviceToDevice,
+                                 stream));
+        HIP_CHECK(hipEventRecord(ev_snap_, stream));
+        HIP_CHECK(hipStreamWaitEvent(roll_stream_, ev_snap_, 0));
+        collect_pending_ = true;
+        collect_episodes_ = episodes;
+        if (roll_kind_ == ROLL_GOAL)    // the window's totals, as a run's
+            HIP_CHECK(hipMemsetAsync(goal_st_.ep_state + 5, 0, 3 * 8,
+                                     roll_stream_));
+        if (use_graph) {
+            if (!stage_graph_exec) {
+                HIP_CHECK(hipStreamBeginCapture(
+                    roll_stream_, hipStreamCaptureModeThreadLocal));
+                enqueue_episode(true, true);
+                HIP_CHECK(hipStreamEndCapture(roll_stream_, &stage_graph));
+                HIP_CHECK(hipGraphInstantiate(&stage_graph_exec, stage_graph,
+                                              nullptr, nullptr, 0));
+            }
+            for (int e = 0; e < episodes; ++e)
+                HIP_CHECK(hipGraphLaunch(stage_graph_exec, roll_stream_));
+        } else {
+            for (int e = 0; e < episodes; ++e) enqueue_episode(true, true);
+        }
+        HIP_CHECK(hipEventRecord(ev_done_, roll_stream_));
+    }
+
+    struct CollectTotals { long long env_steps, rows; };
+
+    // move the window's rows into the live ring on the learner stream, and
+    // wait for it
+    CollectTotals collect_commit() {
+        if (!collect_pending_)
+            throw std::runtime_error(
+                "collect_commit: no collection window is open");
+        HIP_CHECK(hipStreamWaitEvent(stream, ev_done_, 0));
+        const RollCore& c = roll_core();
+        StageArgs a{};
+        a.ss = st_rs; a.sa = st_ra; a.sr = st_rr; a.ss2 = st_rs2;
+        a.sd = st_rd;
+        a.stage_cnt = st_cnt;
+        a.rs = ws.rs; a.ra = ws.ra; a.rr = ws.rr; a.rs2 = ws.rs2;
+        a.rd = ws.rd;
+        a.sum_tree = ws.sum_tree; a.min_tree = ws.min_tree;
+        a.tree_cap = ws.tree_cap; a.capacity = cfg.capacity;
+        a.cnt = ws.cnt;
+        a.ep_state = c.ep_state;
+        a.obs = cfg.obs; a.act = cfg.act;
+        a.per_alpha = cfg.per_alpha;
+        // sized for the staging store, not the (device-side) row count
+        const long work = stage_rows_ * (cfg.obs > 4 ? cfg.obs / 4 : 1);
+        int wgs = ceil_div(work, 256);
+        hipLaunchKernelGGL(k_stage_commit, dim3(wgs > 1024 ? 1024 : wgs),
+                           dim3(256), 0, stream, a);
+        launch_tree_rebuild(1024);
+        hipLaunchKernelGGL(k_stage_commit_end, dim3(1), dim3(64), 0, stream,
+                           a);
+        // the window is closed once its work is enqueued, whatever the
+        // synchronise reports
+        collect_pending_ = false;
+        HIP_CHECK(hipStreamSynchronize(stream));
+        long long w[8];
+        HIP_CHECK(hipMemcpy(w, c.ep_state, sizeof(w),
+                            hipMemcpyDeviceToHost));
+        CollectTotals t{};
+        t.rows = w[2];
+        t.env_steps = roll_kind_ == ROLL_GOAL
+            ? w[7] : (long long)collect_episodes_ * c.horizon * c.M;
+        return t;
+    }
+
     // ---------------- Pendulum rollout (engine_rollout.hip) --------------
     void rollout_alloc(int M, int nsteps, int horizon, float gamma,
                        int noise_kind, float eps, float ou_theta,
@@ -1037,32 +1309,34 @@ public:
         roll_kind_ = ROLL_PENDULUM;
     }
 
-    void pendulum_enqueue_ticks(bool reset) {
-        RollArgs& a = roll_;
+    void pendulum_enqueue_ticks(RollArgs& a, bool reset, hipStream_t st,
+                                const float* slab) {
         int wgs = ceil_div(a.M, 256);
         if (reset)
             hipLaunchKernelGGL(k_roll_reset, dim3(wgs), dim3(256), 0,
-                               stream, a);
+                               st, a);
         int emit_k = 0;
         for (int t = 0; t < a.horizon; ++t) {
-            roll_fwd_chain(a.obs, a.act, a.M);
+            roll_fwd_chain(a.obs, a.act, a.M, st, slab);
             int ek = (t >= a.n - 1) ? emit_k : -1;
             int done = (t == a.horizon - 1) ? 1 : 0;
-            hipLaunchKernelGGL(k_roll_tick, dim3(wgs), dim3(256), 0, stream,
+            hipLaunchKernelGGL(k_roll_tick, dim3(wgs), dim3(256), 0, st,
                                a, t, t % a.n, ek, done);
             if (ek >= 0) ++emit_k;
         }
-        hipLaunchKernelGGL(k_roll_end, dim3(1), dim3(64), 0, stream,
+        hipLaunchKernelGGL(k_roll_end, dim3(1), dim3(64), 0, st,
                            (RollCore&)a, (long)emit_k * a.M);
     }
 
     void rollout_run(int episodes, bool reset, bool use_graph) {
         roll_require(ROLL_PENDULUM, "rollout_alloc first");
+        refuse_in_window("rollout_run");
         run_episodes(episodes, reset, use_graph);
     }
 
     // test hook: inject exact env state (parity vs the numpy oracle)
     void rollout_set_state(const float* th, const float* td, int M) {
+        refuse_in_window("rollout_set_state");
         if (roll_kind_ != ROLL_PENDULUM || M != roll_.M)
             throw std::runtime_error("rollout_set_state: bad M");
         HIP_CHECK(hipMemcpy(roll_.th, th, M * 4, hipMemcpyHostToDevice));
@@ -1121,25 +1395,25 @@ public:
         roll_kind_ = ROLL_GOAL;
     }
 
-    void goal_enqueue_ticks(bool reset) {
-        GoalRollArgs& a = goal_;
+    void goal_enqueue_ticks(GoalRollArgs& a, bool reset, hipStream_t st,
+                            const float* slab) {
         int wgs = ceil_div(a.M, 256);
         if (reset)
             hipLaunchKernelGGL(k_goal_reset, dim3(wgs), dim3(256), 0,
-                               stream, a);
+                               st, a);
         for (int t = 0; t < a.horizon; ++t) {
-            roll_fwd_chain(a.obs, a.act, a.M);
-            hipLaunchKernelGGL(k_goal_tick, dim3(wgs), dim3(256), 0, stream,
+            roll_fwd_chain(a.obs, a.act, a.M, st, slab);
+            hipLaunchKernelGGL(k_goal_tick, dim3(wgs), dim3(256), 0, st,
                                a, t);
         }
-        hipLaunchKernelGGL(k_goal_count, dim3(wgs), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(k_goal_count, dim3(wgs), dim3(256), 0, st, a);
         hipLaunchKernelGGL(k_goal_scan, dim3(1), dim3(GOAL_SCAN_THREADS), 0,
-                           stream, a);
+                           st, a);
         // one wave per env, four to a workgroup
         int ewgs = ceil_div(a.M, 4);
         hipLaunchKernelGGL(k_goal_emit, dim3(ewgs > 2048 ? 2048 : ewgs),
-                           dim3(256), 0, stream, a);
-        hipLaunchKernelGGL(k_goal_end, dim3(1), dim3(64), 0, stream, a);
+                           dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_goal_end, dim3(1), dim3(64), 0, st, a);
     }
 
     // Totals over the episodes of one goal_rollout_run call, read from the
@@ -1148,6 +1422,7 @@ public:
 
     GoalTotals goal_rollout_run(int episodes, bool reset, bool use_graph) {
         roll_require(ROLL_GOAL, "goal_rollout_alloc first");
+        refuse_in_window("goal_rollout_run");
         HIP_CHECK(hipMemsetAsync(goal_.ep_state + 5, 0, 3 * 8, stream));
         run_episodes(episodes, reset, use_graph);
         long long w[3];
@@ -1159,6 +1434,7 @@ public:
     // test hook: inject exact env state, leaving everything else as
     // k_goal_reset leaves it
     void goal_rollout_set_state(const float* pos, const float* goal, int M) {
+        refuse_in_window("goal_rollout_set_state");
         if (roll_kind_ != ROLL_GOAL || M != goal_.M)
             throw std::runtime_error("goal_rollout_set_state: bad M");
         const int D = goal_.D;
@@ -1229,8 +1505,8 @@ public:
         roll_kind_ = ROLL_SYNTH;
     }
 
-    void synth_enqueue_ticks(bool reset) {
-        SynRollArgs& a = syn_;
+    void synth_enqueue_ticks(SynRollArgs& a, bool reset, hipStream_t st,
+                             const float* slab) {
         const long elems = (long)a.M * (a.O > a.A ? a.O : a.A);
         int wgs = ceil_div(elems, 256);
         if (wgs > 2048) wgs = 2048;
@@ -1238,36 +1514,38 @@ public:
         int twgs = ceil_div(a.M, 4);
         if (twgs > 2048) twgs = 2048;
         if (reset)
-            hipLaunchKernelGGL(k_syn_reset, dim3(wgs), dim3(256), 0, stream,
+            hipLaunchKernelGGL(k_syn_reset, dim3(wgs), dim3(256), 0, st,
                                a);
         FwdJob mix = fwd_job(a.obs, a.act_env, syn_dyn_, syn_dyn_desc_, a.z,
                              ACT_NONE, a.M);
         int emit_k = 0;
         for (int t = 0; t < a.horizon; ++t) {
-            roll_fwd_chain(a.obs, a.act, a.M);
+            roll_fwd_chain(a.obs, a.act, a.M, st, slab);
             int slot = t % a.n;
-            hipLaunchKernelGGL(k_syn_act, dim3(wgs), dim3(256), 0, stream, a,
+            hipLaunchKernelGGL(k_syn_act, dim3(wgs), dim3(256), 0, st, a,
                                t, slot);
-            if (fwd_uses_mfma(a.M)) launch_fwd_mfma(mix);
-            else launch_fwd_valu(mix);
+            if (fwd_uses_mfma(a.M)) launch_fwd_mfma(mix, false, st);
+            else launch_fwd_valu(mix, st);
             int ek = (t >= a.n - 1) ? emit_k : -1;
             int done = (t == a.horizon - 1) ? 1 : 0;
-            hipLaunchKernelGGL(k_syn_tick, dim3(twgs), dim3(256), 0, stream,
+            hipLaunchKernelGGL(k_syn_tick, dim3(twgs), dim3(256), 0, st,
                                a, t, slot, ek, done);
             if (ek >= 0) ++emit_k;
         }
-        hipLaunchKernelGGL(k_roll_end, dim3(1), dim3(64), 0, stream,
+        hipLaunchKernelGGL(k_roll_end, dim3(1), dim3(64), 0, st,
                            (RollCore&)a, (long)emit_k * a.M);
     }
 
     void synth_rollout_run(int episodes, bool reset, bool use_graph) {
         roll_require(ROLL_SYNTH, "synth_rollout_alloc first");
+        refuse_in_window("synth_rollout_run");
         run_episodes(episodes, reset, use_graph);
     }
 
     // test hook: inject exact env state, leaving the OU process as
     // k_syn_reset leaves it
     void synth_rollout_set_state(const float* state, int M) {
+        refuse_in_window("synth_rollout_set_state");
         if (roll_kind_ != ROLL_SYNTH || M != syn_.M)
             throw std::runtime_error("synth_rollout_set_state: bad M");
         HIP_CHECK(hipMemcpy(syn_.obs, state, (long)M * syn_.O * 4,
@@ -1371,7 +1649,8 @@ public:
         int wgs = ceil_div(E, 256);
         hipLaunchKernelGGL(k_eval_begin, dim3(1), dim3(64), 0, stream, a);
         auto chain = [&] {
-            roll_fwd_chain(a.obs, a.act, E, e_h1, e_h2, e_h3);
+            roll_fwd_chain(a.obs, a.act, E, e_h1, e_h2, e_h3, stream,
+                           ws.p_actor);
         };
         if (roll_kind_ == ROLL_PENDULUM) {
             if (reset)

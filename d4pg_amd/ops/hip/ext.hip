@@ -57,6 +57,8 @@ static py::dict info(int64_t h) {
     d["gemm_precision"] = e.cfg.gemm_bf16 ? "bf16" : "fp32";
     d["persistent"] = e.step_path() == Engine::PATH_PERSISTENT;
     d["seed"] = (int64_t)e.cfg.seed;
+    // episodes one collection window can hold; 0 before collect_alloc
+    d["collect_max_episodes"] = e.collect_max_episodes_;
     py::list al, cl;
     for (int i = 0; i < 4; ++i) {
         py::dict ld;
@@ -135,6 +137,7 @@ static void ingest(int64_t h, torch::Tensor s, torch::Tensor a,
 // the same convention Engine::alloc establishes at step 0)
 static void set_seed(int64_t h, int64_t seed) {
     Engine& e = get(h);
+    e.refuse_in_window("set_seed");
     e.cfg.seed = e.ws.seed = (uint64_t)seed;
     // the seed is baked into captured kernel ARGUMENTS (k_per_sample /
     // k_step_persistent take it by value), so a previously captured
@@ -158,6 +161,7 @@ static void set_schedule(int64_t h, int64_t steps_done, double max_priority) {
 // length on uniform replay)
 static py::dict replay_state(int64_t h) {
     Engine& e = get(h);
+    e.refuse_in_window("replay_state (state save)");
     Counters c{};
     HIP_CHECK(hipMemcpy(&c, e.ws.cnt, sizeof(c), hipMemcpyDeviceToHost));
     long n = c.size;
@@ -197,6 +201,7 @@ static void load_replay_state(int64_t h, torch::Tensor s, torch::Tensor a,
                               torch::Tensor min_tree, int64_t size,
                               int64_t pos, double max_priority) {
     Engine& e = get(h);
+    e.refuse_in_window("load_replay_state (state load)");
     const int O = e.cfg.obs, A = e.cfg.act;
     long n = size;
     TORCH_CHECK(sum_tree.numel() == 2 * e.ws.tree_cap &&
@@ -441,6 +446,27 @@ static py::dict synth_rollout_info(int64_t h) {
     return d;
 }
 
+// ---- overlapped collection (engine_stage.hip) ----
+static void collect_alloc(int64_t h, int64_t max_episodes) {
+    if (max_episodes < 1 || max_episodes > (1 << 30))
+        throw std::runtime_error("collect_alloc: max_episodes < 1");
+    get(h).collect_alloc((int)max_episodes);
+}
+
+static void collect_begin(int64_t h, int64_t episodes, bool use_graph) {
+    // clamped before the narrowing cast; the engine refuses both ends
+    episodes = std::min<int64_t>(std::max<int64_t>(episodes, 0), 1 << 30);
+    get(h).collect_begin((int)episodes, use_graph);
+}
+
+// (env_steps, rows) of the committed window
+static py::tuple collect_commit(int64_t h) {
+    Engine::CollectTotals t = get(h).collect_commit();
+    return py::make_tuple((int64_t)t.env_steps, (int64_t)t.rows);
+}
+
+static bool collect_pending(int64_t h) { return get(h).collect_pending_; }
+
 // ---- device greedy evaluation (engine_eval.hip) ----
 static void eval_alloc(int64_t h, int64_t E, int64_t horizon, bool has_seed,
                        int64_t seed, bool fixed_starts) {
@@ -617,6 +643,18 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
         {"sum_tree", {e.ws.sum_tree, {2 * e.ws.tree_cap}, false, true}},
         {"min_tree", {e.ws.min_tree, {2 * e.ws.tree_cap}, false, true}},
     };
+    if (e.stage_pool_) {
+        // the actor snapshot and the staging store of an overlapped
+        // collection (whole store; rows past the staged count are stale)
+        const long S = e.stage_rows_;
+        m.insert({{"p_actor_roll",
+                   {e.p_actor_roll, {e.anet.n_params}, false, false}},
+                  {"stage_s", {e.st_rs, {S, O}, false, false}},
+                  {"stage_a", {e.st_ra, {S, A}, false, false}},
+                  {"stage_r", {e.st_rr, {S}, false, false}},
+                  {"stage_s2", {e.st_rs2, {S, O}, false, false}},
+                  {"stage_d", {e.st_rd, {S}, false, false}}});
+    }
     auto it = m.find(name);
     if (it == m.end()) throw std::runtime_error("unknown buffer " + name);
     auto& ent = it->second;
@@ -688,6 +726,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("synth_rollout_run", &d4pg::synth_rollout_run);
     mod.def("synth_rollout_set_state", &d4pg::synth_rollout_set_state);
     mod.def("synth_rollout_info", &d4pg::synth_rollout_info);
+    mod.def("collect_alloc", &d4pg::collect_alloc);
+    mod.def("collect_begin", &d4pg::collect_begin);
+    mod.def("collect_commit", &d4pg::collect_commit);
+    mod.def("collect_pending", &d4pg::collect_pending);
     mod.def("eval_alloc", &d4pg::eval_alloc);
     mod.def("eval_run", &d4pg::eval_run);
     mod.def("eval_results", &d4pg::eval_results);

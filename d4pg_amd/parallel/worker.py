@@ -42,6 +42,19 @@ class Worker:
         self._device_run = None     # the allocated producer's run method
         self.device_rows = 0        # replay rows the device episodes wrote
         self._device_kind = self._find_device_kind()
+        # --async_collect 1: collection windows overlap the train cycle
+        self._async = bool(int(getattr(args, "async_collect", 0)))
+        if self._async and self._device_kind is None:
+            raise ValueError(
+                "--async_collect 1 overlaps DEVICE collection with training: "
+                "it needs --backend hip, --vector_envs M > 0, --gpu_actors "
+                "!= 0 and an env a device rollout models (Pendulum, "
+                "GoalReach with --her 1, a synthetic env); got backend %r, "
+                "--vector_envs %d, --gpu_actors %d, --env %r, --her %d"
+                % (getattr(agent, "backend", "eager"),
+                   int(getattr(args, "vector_envs", 0)),
+                   int(getattr(args, "gpu_actors", -1)),
+                   getattr(args, "env", None), int(getattr(args, "her", 0))))
 
     # -- the closed on-GPU cycle --
     # With backend 'hip', --vector_envs M > 0, --gpu_actors != 0 and an env
@@ -52,6 +65,14 @@ class Worker:
     # policy is the p_actor slab the step updates (no parameter copy, no host
     # rows) and env.step is never called.  Episode counts round up to whole
     # batches of M envs.
+    #
+    # With --async_collect 1 the warmup stays serial and each cycle becomes
+    # collect_begin(ceil(episodes_per_cycle / M)) -> train_cycle ->
+    # collect_commit -> evaluate: the episodes run on the engine's rollout
+    # stream with a snapshot of the actor while the learner trains, and
+    # their rows enter the replay at the commit.  Rows collected with the
+    # policy of cycle k are therefore sampled from cycle k+1 on (an actor
+    # one window behind the learner, as across the distributed ranks).
     eval_fixed_starts = False   # common random numbers across evaluations
 
     def _find_device_kind(self):
@@ -93,7 +114,28 @@ class Worker:
         self._device_run = alloc_producer(eng, kind, a, self.env, m, seed)
         eng.eval_alloc(int(a.eval_trials), horizon=horizon,
                        fixed_starts=self.eval_fixed_starts)
+        if self._async:
+            eng.collect_alloc(self._window_episodes())
         return eng
+
+    def _window_episodes(self) -> int:
+        """Device episodes of one collection window: episodes_per_cycle
+        rounded up to whole batches of M envs."""
+        return -(-int(self.args.episodes_per_cycle)
+                 // int(self.args.vector_envs))
+
+    def collect_begin(self) -> None:
+        """Open the cycle's collection window (returns at once)."""
+        eng = self.device_engine()
+        self.agent.replayBuffer.flush()
+        eng.collect_begin(self._window_episodes())
+
+    def collect_commit(self) -> None:
+        """Close the window: its rows enter the replay after the cycle's
+        train steps."""
+        out = self.device_engine().collect_commit()
+        self.env_meter.add(int(out[0]))
+        self.device_rows += int(out[1])
 
     def _device_collect(self, episodes: int) -> None:
         if episodes <= 0:
@@ -168,8 +210,13 @@ class Worker:
         cycle_idx = 0
         for epoch in range(self.args.n_eps):
             for _ in range(self.args.cycles_per_epoch):
-                self.collect_cycle()
-                self.train_cycle(global_model, global_count)
+                if self._async:
+                    self.collect_begin()
+                    self.train_cycle(global_model, global_count)
+                    self.collect_commit()
+                else:
+                    self.collect_cycle()
+                    self.train_cycle(global_model, global_count)
                 avg_r, succ = self.evaluate()
                 step = (global_count.item() if global_count is not None
                         else self.agent.train_steps_done)
