@@ -53,8 +53,16 @@ class DDPG:
                  n_steps=1, *, device="cpu", backend="eager", hidden=256,
                  is_weighting=False, true_td_priorities=False, seed=None,
                  noise="gaussian", noise_eps=0.3, ou_theta=0.15,
-                 ou_sigma=0.2, ou_mu=0.0, gemm_precision="fp32"):
+                 ou_sigma=0.2, ou_mu=0.0, gemm_precision="fp32",
+                 max_grad_norm=0.0):
         check_gemm_precision(gemm_precision)
+        # global-norm gradient clipping, actor and critic separately (each
+        # has its own optimizer); 0 = off.  Both backends.
+        max_grad_norm = float(max_grad_norm)
+        if not max_grad_norm >= 0.0:
+            raise ValueError("max_grad_norm must be >= 0 (0 = off), got %r"
+                             % max_grad_norm)
+        self.max_grad_norm = max_grad_norm
         if gemm_precision == "bf16" and backend != "hip":
             raise ValueError(
                 "gemm_precision='bf16' is a mode of the hip backend's wide "
@@ -286,11 +294,13 @@ class DDPG:
             global_model.critic.zero_grad()
         qdist_loss.backward()
         if global_model is not None:
+            self._clip_grads(self.critic)
             self.copy_gradients(self.critic, global_model.critic)
             self.optimizer_global_critic.step()
         else:
             if self.grad_sync is not None:
                 self.grad_sync(self.critic)
+            self._clip_grads(self.critic)
             self.optimizer_critic.step()
 
         # -- actor update --
@@ -302,12 +312,14 @@ class DDPG:
             global_model.actor.zero_grad()
         policy_loss.backward()
         if global_model is not None:
+            self._clip_grads(self.actor)
             self.copy_gradients(self.actor, global_model.actor)
             self.optimizer_global_actor.step()
             self.sync_local_global(global_model)
         else:
             if self.grad_sync is not None:
                 self.grad_sync(self.actor)
+            self._clip_grads(self.actor)
             self.optimizer_actor.step()
 
         self.update_target_parameters()
@@ -318,6 +330,15 @@ class DDPG:
 
         self.train_steps_done += 1
         return float(qdist_loss.detach()), float(policy_loss.detach())
+
+    def _clip_grads(self, module) -> None:
+        """Clip one net's gradients by global norm, right before its
+        optimizer step: after the data-parallel all-reduce (the norm of the
+        reduced gradient, as on the engine) and, in the HogWild path, before
+        the gradients are handed to the global model."""
+        if self.max_grad_norm > 0.0:
+            torch.nn.utils.clip_grad_norm_(module.parameters(),
+                                           self.max_grad_norm)
 
     def ensure_engine(self):
         """Build the fused HIP engine bridge now (backend='hip') instead of on

@@ -133,6 +133,13 @@ def make_parser() -> argparse.ArgumentParser:
                         "operands to bf16 and accumulates in fp32; weights, "
                         "Adam state and the replay stay fp32.  Refused by "
                         "the eager backend and at --bsize <= 512")
+    p.add_argument("--clip_grad_norm", default=0.0, type=float,
+                   help="global-norm gradient clipping threshold, applied "
+                        "to the actor's and to the critic's gradient "
+                        "separately before each Adam step (the rule of "
+                        "torch.nn.utils.clip_grad_norm_), on both backends; "
+                        "0 = off.  With the hip backend the Worker then "
+                        "also logs grad_norm_actor / grad_norm_critic")
     p.add_argument("--her_ratio", default=0.8, type=float,
                    help="probability that a step also stores a hindsight "
                         "('future' strategy) copy when --her 1")
@@ -232,6 +239,7 @@ class D4PGConfig:
     her_ratio: float = 0.8
     gemm_precision: str = "fp32"
     async_collect: int = 0
+    clip_grad_norm: float = 0.0
     extra: dict = field(default_factory=dict)
 
     @classmethod

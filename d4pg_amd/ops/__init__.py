@@ -183,7 +183,7 @@ class FusedEngine:
                  per_alpha=0.6, per_beta0=0.4, per_beta_iters=100000,
                  per_eps=1e-6, seed=0, is_weighting=False,
                  prioritized=True, true_td_priorities=False,
-                 gemm_precision="fp32"):
+                 gemm_precision="fp32", max_grad_norm=0.0):
         """prioritized=False: uniform replay (an integer philox draw per
         probe, IS weights exactly 1, no sum/min trees allocated or
         maintained).  true_td_priorities: the written-back priority is
@@ -192,7 +192,13 @@ class FusedEngine:
         (batch > 512) round both operands to bf16 and accumulate in fp32;
         parameters, moments, activations and the replay stay fp32, and so do
         the rollout and evaluation forwards (ARCHITECTURE.md, "bf16 wide
-        path").  The engine refuses it at batch <= 512."""
+        path").  The engine refuses it at batch <= 512.  max_grad_norm > 0:
+        global-norm gradient clipping, the rule of
+        torch.nn.utils.clip_grad_norm_ applied to the actor and to the
+        critic separately, on all three train paths; Adam consumes the
+        scaled gradient while g_actor / g_critic keep the raw one
+        (ARCHITECTURE.md, "Gradient clipping").  0 is off; the engine
+        refuses a negative or NaN threshold."""
         check_gemm_precision(gemm_precision)
         self.ext = load_extension()
         self.h = self.ext.create(
@@ -201,8 +207,10 @@ class FusedEngine:
             float(lr_actor), float(lr_critic), float(per_alpha),
             float(per_beta0), int(per_beta_iters), float(per_eps),
             int(seed), bool(is_weighting), bool(prioritized),
-            bool(true_td_priorities), gemm_precision == "bf16")
+            bool(true_td_priorities), gemm_precision == "bf16",
+            float(max_grad_norm))
         self.batch = batch
+        self.max_grad_norm = float(max_grad_norm)
         self.gemm_precision = gemm_precision
         self.prioritized = bool(prioritized)
         self._captured = 0
@@ -311,6 +319,15 @@ class FusedEngine:
     # -- introspection / resume --
     def counters(self):
         return self.ext.counters(self.h)
+
+    def grad_stats(self):
+        """Gradient norms and clip scales of the last train step:
+        norm_actor / norm_critic (float64, of the raw gradient slabs) and
+        scale_actor / scale_critic (float32, what Adam multiplied by).
+        All zero on an engine without clipping, which never computes them.
+        One small device-to-host copy; call after the step has been
+        synchronised."""
+        return dict(self.ext.grad_stats(self.h))
 
     def set_schedule(self, steps_done, max_priority=1.0):
         """Restore schedule counters to 'steps_done completed' (resume).
@@ -555,6 +572,7 @@ class FusedDDPGBridge:
             prioritized=ddpg.prioritized_replay,
             true_td_priorities=ddpg.true_td_priorities,
             gemm_precision=ddpg.gemm_precision,
+            max_grad_norm=ddpg.max_grad_norm,
             seed=0 if ddpg.rng is None else int(ddpg.rng.integers(1 << 31)))
         self.engine.load_from_modules(ddpg.actor, ddpg.actor_target,
                                       ddpg.critic, ddpg.critic_target)

@@ -103,6 +103,9 @@ public:
                 "gemm_precision='bf16' needs batch > 512: only the wide "
                 "train step has bf16 GEMMs, the persistent and row-block "
                 "paths (batch <= 512) are fp32 only");
+        if (!(c.max_grad_norm >= 0.0))      // negative or NaN
+            throw std::runtime_error(
+                "max_grad_norm must be >= 0 (0 turns gradient clipping off)");
         anet = make_actor_net(c.obs, c.act, c.hidden);
         cnet = make_critic_net(c.obs, c.act, c.hidden, c.atoms);
         ws.B = c.batch; ws.O = c.obs; ws.A = c.act; ws.H = c.hidden;
@@ -115,6 +118,7 @@ public:
         ws.is_weighting = c.is_weighting;
         ws.prioritized = c.prioritized; ws.true_td = c.true_td;
         ws.seed = c.seed;
+        ws.max_grad_norm = c.max_grad_norm;
         ws.tree_cap = has_trees() ? next_pow2(c.capacity) : 0;
         ws.n_actor = anet.n_params; ws.n_critic = cnet.n_params;
         for (int i = 0; i < 4; ++i) {
@@ -130,7 +134,8 @@ public:
         hipDeviceProp_t prop;
         HIP_CHECK(hipGetDeviceProperties(&prop, dev));
         HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, k_step_persistent, 256, 0));
+            &per_cu, clip() ? k_step_persistent<true>
+                            : k_step_persistent<false>, 256, 0));
         persistent_fits_ = (long)per_cu * prop.multiProcessorCount >= PNWG;
         device_ = dev;
         alloc();
@@ -145,6 +150,11 @@ public:
     // step samples by integer draw and skips the priority write-back, and
     // the write side copies rows only.
     bool has_trees() const { return cfg.prioritized != 0; }
+
+    // Global-norm gradient clipping is on: the one predicate behind the
+    // clip-on kernels and launches.  Off, every launch sequence is the
+    // plain one.
+    bool clip() const { return cfg.max_grad_norm > 0.0; }
 
     // internal tree nodes from the leaves: one bandwidth-bound sweep per
     // level (bulk ingest, synth_fill, once per rollout episode)
@@ -313,6 +323,11 @@ public:
         ing_r = carve<float>(ing_cap, off);
         ing_s2 = carve<float>((long)ing_cap * O, off);
         ing_d = carve<float>(ing_cap, off);
+        // gradient clipping: statistics block and per-chunk partials (last,
+        // so every other buffer keeps its offset)
+        ws.gstat = carve<GradStats>(1, off);
+        ws.gn_part_a = carve<double>(gn_chunks(pa), off);
+        ws.gn_part_c = carve<double>(gn_chunks(pc), off);
         return off;
     }
 
@@ -513,8 +528,12 @@ public:
     }
 
     void enqueue_persistent(int nsteps) {
-        hipLaunchKernelGGL(k_step_persistent, dim3(PNWG), dim3(256), 0,
-                           stream, ws, nsteps);
+        if (clip())
+            hipLaunchKernelGGL(k_step_persistent<true>, dim3(PNWG),
+                               dim3(256), 0, stream, ws, nsteps);
+        else
+            hipLaunchKernelGGL(k_step_persistent<false>, dim3(PNWG),
+                               dim3(256), 0, stream, ws, nsteps);
     }
 
     // All four layers' weight gradients of one net in a single k_bwd4
@@ -543,8 +562,34 @@ public:
                            dim3(256), 0, stream, ws);
     }
 
-    // Adam + target soft-update of one net, fused
+    // Adam + target soft-update of one net, fused.  With clipping on, the
+    // net's gradient norm and scale come first (inside PH_*_APPLY, so after
+    // a data-parallel all-reduce, and inside captured graphs) and the
+    // clip-on Adam kernel reads the scale from the statistics block.
     void launch_adam_lerp(bool is_actor) {
+        if (clip()) {
+            const float* g = is_actor ? ws.g_actor : ws.g_critic;
+            double* part = is_actor ? ws.gn_part_a : ws.gn_part_c;
+            const long n = is_actor ? anet.n_params : cnet.n_params;
+            hipLaunchKernelGGL(k_grad_norm, dim3(gn_chunks(n)), dim3(256), 0,
+                               stream, g, n, part);
+            hipLaunchKernelGGL(k_grad_finish, dim3(1), dim3(64), 0, stream,
+                               part, n, cfg.max_grad_norm, ws.gstat,
+                               is_actor ? 1 : 0);
+            if (is_actor)
+                hipLaunchKernelGGL(k_adam_lerp_clip, dim3(256), dim3(256), 0,
+                                   stream, ws.p_actor, ws.g_actor, ws.m_actor,
+                                   ws.v_actor, ws.p_actor_t, anet.n_params,
+                                   cfg.lr_actor, 0.9f, 0.999f, 1e-8f, cfg.tau,
+                                   ws.cnt, 1, ws.gstat);
+            else
+                hipLaunchKernelGGL(k_adam_lerp_clip, dim3(256), dim3(256), 0,
+                                   stream, ws.p_critic, ws.g_critic,
+                                   ws.m_critic, ws.v_critic, ws.p_critic_t,
+                                   cnet.n_params, cfg.lr_critic, 0.9f, 0.999f,
+                                   1e-8f, cfg.tau, ws.cnt, 0, ws.gstat);
+            return;
+        }
         if (is_actor)
             hipLaunchKernelGGL(k_adam_lerp, dim3(256), dim3(256), 0, stream,
                                ws.p_actor, ws.g_actor, ws.m_actor, ws.v_actor,
@@ -864,6 +909,14 @@ public:
     }
     void store_slab(float* dst, const float* src, long n) {
         HIP_CHECK(hipMemcpy(dst, src, n * 4, hipMemcpyDeviceToHost));
+    }
+
+    // norms and scales of the last step; zeros when clipping is off (the
+    // block is cleared at allocation and never written)
+    GradStats read_grad_stats() {
+        GradStats h{};
+        HIP_CHECK(hipMemcpy(&h, ws.gstat, sizeof(h), hipMemcpyDeviceToHost));
+        return h;
     }
 
     Counters read_counters() {

@@ -84,6 +84,7 @@ struct EngineCfg {
     int true_td = 0;           // priority |E_m[z] - E_q[z]| for <m, q>
     int gemm_bf16 = 0;         // wide train step: bf16 MFMA operands (RNE),
                                // fp32 accumulate; batch > 512 only
+    double max_grad_norm = 0;  // global-norm gradient clip, per net; 0: off
 };
 
 // device-side counters (one small block)
@@ -97,6 +98,14 @@ struct Counters {
     float max_priority;
     float loss_critic;         // per-step scalars (overwritten each step)
     float loss_actor;
+};
+
+// Gradient-clip statistics of the last step (written only when clipping is
+// on; zero otherwise).  Derived state: not checkpointed, and deliberately not
+// part of Counters, whose layout the staging counters and checkpoints share.
+struct GradStats {
+    double norm_actor, norm_critic;    // global L2 norm of the raw gradient
+    float scale_actor, scale_critic;   // min(1, max_grad_norm / (norm + 1e-6))
 };
 
 // max fan-in a fwd workgroup stages (hidden(1024) + act margin)
@@ -175,6 +184,12 @@ struct StepArgs {
     unsigned long long* gbar;        // persistent grid barrier state
     unsigned long long* tstamp;      // [64] per-phase s_memrealtime stamps
     float *da, *pda;                 // action-slice deltas (wide path)
+    // gradient clipping (max_grad_norm > 0): per-chunk double sums of
+    // squares of g_actor / g_critic (ceil(n / GN_CHUNK) each) and the
+    // norm / scale block of the last step
+    double max_grad_norm;
+    double *gn_part_a, *gn_part_c;
+    GradStats* gstat;
 };
 
 

@@ -169,16 +169,22 @@ __global__ void k_tanh_bwd(const float* __restrict__ da,
 
 // ---- fused Adam + target soft-update in one pass (row-block, wide) ---------
 // (the element update is written out here and in p_adam_lerp, see adam_bias)
-__global__ void k_adam_lerp(float* __restrict__ p, const float* __restrict__ g,
-                            float* __restrict__ m, float* __restrict__ v,
-                            float* __restrict__ tgt, long n, float lr,
-                            float b1, float b2, float eps, float tau,
-                            const Counters* cnt, int is_actor) {
+// CLIP: the gradient enters as scale * g[i], rounded once into gi before the
+// update reads it (an explicit multiply, never contracted into the update:
+// at scale 1.0 the clip-on form is bitwise the plain one).  The slab g keeps
+// the raw gradient.
+template <bool CLIP>
+__device__ __forceinline__ void adam_lerp_grid(
+        float* __restrict__ p, const float* __restrict__ g,
+        float* __restrict__ m, float* __restrict__ v,
+        float* __restrict__ tgt, long n, float lr, float b1, float b2,
+        float eps, float tau, const Counters* cnt, int is_actor,
+        float scale) {
     AdamBias bc = adam_bias(b1, b2, is_actor ? cnt->adam_t_actor
                                              : cnt->adam_t_critic);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long)gridDim.x * blockDim.x) {
-        float gi = g[i];
+        float gi = CLIP ? __fmul_rn(scale, g[i]) : g[i];
         float mi = b1 * m[i] + (1.f - b1) * gi;
         float vi = b2 * v[i] + (1.f - b2) * gi * gi;
         m[i] = mi; v[i] = vi;
@@ -186,6 +192,46 @@ __global__ void k_adam_lerp(float* __restrict__ p, const float* __restrict__ g,
         p[i] = pn;
         tgt[i] += tau * (pn - tgt[i]);
     }
+}
+
+__global__ void k_adam_lerp(float* __restrict__ p, const float* __restrict__ g,
+                            float* __restrict__ m, float* __restrict__ v,
+                            float* __restrict__ tgt, long n, float lr,
+                            float b1, float b2, float eps, float tau,
+                            const Counters* cnt, int is_actor) {
+    adam_lerp_grid<false>(p, g, m, v, tgt, n, lr, b1, b2, eps, tau, cnt,
+                          is_actor, 1.f);
+}
+
+// The clip-on instantiation: the scale is read from the statistics block
+// k_grad_finish wrote just before (device memory, because it changes per
+// step under graph replay).
+__global__ void k_adam_lerp_clip(float* __restrict__ p,
+                                 const float* __restrict__ g,
+                                 float* __restrict__ m, float* __restrict__ v,
+                                 float* __restrict__ tgt, long n, float lr,
+                                 float b1, float b2, float eps, float tau,
+                                 const Counters* cnt, int is_actor,
+                                 const GradStats* st) {
+    adam_lerp_grid<true>(p, g, m, v, tgt, n, lr, b1, b2, eps, tau, cnt,
+                         is_actor,
+                         is_actor ? st->scale_actor : st->scale_critic);
+}
+
+// ---- global-norm gradient clipping (row-block, wide) -------------------------
+// One workgroup per GN_CHUNK chunk of the slab, then a one-workgroup finish:
+// the two helpers of engine_rowmath.hip the persistent kernel calls too.
+__global__ void __launch_bounds__(256)
+k_grad_norm(const float* __restrict__ g, long n, double* gn_part) {
+    __shared__ double red[256];
+    grad_sumsq_chunk(g, n, (int)blockIdx.x, gn_part, red);
+}
+
+__global__ void k_grad_finish(const double* gn_part, long n, double max_norm,
+                              GradStats* st, int is_actor) {
+    if (threadIdx.x == 0)
+        grad_stats_write(st, is_actor,
+                         grad_clip_finish(gn_part, n, max_norm));
 }
 
 }  // namespace d4pg

@@ -201,6 +201,13 @@ __device__ inline void t_bar(unsigned long long* tc,
 // (__noinline__ is load-bearing: inlining 15 copies into the persistent
 // kernel segfaults ROCm 7.2's clang in ADCE; the call overhead is noise
 // next to the ~1 us phase time.)
+// TWIN: each instantiation of k_step_persistent calls its own copy of the two
+// out-of-line helpers (p_fwd, p_dw2), the code being the same.  An
+// out-of-line function shared by two kernels changes the register allocation
+// of both (measured: the default kernel went from 598 to 658 spilled SGPRs
+// and from 84 to 216 B of scratch); with a copy each, the default kernel
+// compiles to exactly what it was before the clip-on one existed.
+template <bool TWIN>
 __device__ __noinline__ void p_fwd(float* lds, const float* x1, const float* x2,
                              const float* wt, const float* bias, float* y,
                              int B, int in1, int in2, int out, int act_kind,
@@ -450,6 +457,7 @@ __device__ inline void p_bwd_dx(float* lds, const float* dz, const float* wt,
 // each thread owns a 4x4 output patch (ig = tid>>4 picks 4 i's, og = tid&15
 // picks 4 o's) — 8 LDS reads + 16 FMAs per batch row.  Bias rows fold in on
 // the i0==0 tiles.  Accumulation over b is ascending.
+template <bool TWIN>                  // see p_fwd
 __device__ __noinline__ void p_dw2(float* lds, const float* dz,
                                    const float* x1, const float* x2,
                                    float* dwt, float* dbias,
@@ -536,13 +544,16 @@ __device__ __noinline__ void p_dw2(float* lds, const float* dz,
     }
 }
 
+// CLIP: the gradient enters as scale * gr[i], rounded once before the update
+// reads it, as in k_adam_lerp_clip; the slab keeps the raw gradient.
+template <bool CLIP>
 __device__ inline void p_adam_lerp(float* __restrict__ p,
                                    const float* __restrict__ gr,
                                    float* __restrict__ m,
                                    float* __restrict__ v,
                                    float* __restrict__ tgt_slab, long n,
                                    float lr, float tau, long long t,
-                                   int nwg = PNWG) {
+                                   float scale, int nwg = PNWG) {
     const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
     AdamBias bc = adam_bias(b1, b2, t);
     // register-batched: fire all 5 streams' loads for 4 grid-strides at
@@ -568,7 +579,7 @@ __device__ inline void p_adam_lerp(float* __restrict__ p,
             if (i >= n) continue;
             // k_adam_lerp's element update, written out in both (see
             // adam_bias for why it is not one helper)
-            float gi = gi_[u];
+            float gi = CLIP ? __fmul_rn(scale, gi_[u]) : gi_[u];
             float mi = b1 * mi_[u] + (1.f - b1) * gi;
             float vi = b2 * vi_[u] + (1.f - b2) * gi * gi;
             m[i] = mi; v[i] = vi;
@@ -578,6 +589,29 @@ __device__ inline void p_adam_lerp(float* __restrict__ p,
             tgt_slab[i] = ti_[u] + tau * (pn - ti_[u]);
         }
     }
+}
+
+// Gradient-clip phase of the clip-on kernel: the workgroups take the slab's
+// GN_CHUNK chunks round-robin and write their double sums of squares to
+// gn_part.  The caller's p_bar publishes them (they cross a grid barrier:
+// plain stores and loads, the hand-off rule); after it every workgroup that
+// runs Adam sums the partials itself (p_grad_scale), so no broadcast is needed.
+__device__ inline void p_grad_sumsq(const float* gr, long n, double* gn_part,
+                                    float* lds) {
+    double* red = reinterpret_cast<double*>(lds);
+    int nc = gn_chunks(n);
+    for (int c = (int)blockIdx.x; c < nc; c += PNWG)
+        grad_sumsq_chunk(gr, n, c, gn_part, red);
+}
+
+// ... and the scale from the published partials; workgroup 0 records it.
+__device__ inline float p_grad_scale(const StepArgs& g, int is_actor) {
+    GradClip c = grad_clip_finish(is_actor ? g.gn_part_a : g.gn_part_c,
+                                  is_actor ? g.n_actor : g.n_critic,
+                                  g.max_grad_norm);
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        grad_stats_write(g.gstat, is_actor, c);
+    return c.scale;
 }
 
 // sample + gather phase, PER or uniform (one wave per probe, like
@@ -690,6 +724,12 @@ __device__ inline void p_per_update(const StepArgs& g, int owner_wg) {
                      [&](int i) { return g.tree_cap + g.bidx[i]; });
 }
 
+// CLIP (max_grad_norm > 0) adds, per net, the chunked sum of squares of the
+// complete gradient slab and ONE more grid barrier between the dW phase and
+// Adam; every one of the PNWG workgroups takes that barrier, under the
+// template parameter alone (grid-uniform by construction, never data).
+// k_step_persistent<false> is the kernel without any of it.
+template <bool CLIP>
 __global__ void __launch_bounds__(256, 1)
 k_step_persistent(StepArgs g, int nsteps) {
     __shared__ float lds[PLDS_FLOATS];
@@ -747,50 +787,50 @@ k_step_persistent(StepArgs g, int nsteps) {
             PTIME(g, s, 1);
             // PH1: four independent L1s (16 wgs each)
             if (wg < PW4)
-                p_fwd(lds, g.bs2, nullptr, at.w1, at.b1, g.at_h1, B, O, 0,
+                p_fwd<CLIP>(lds, g.bs2, nullptr, at.w1, at.b1, g.at_h1, B, O, 0,
                       H, ACT_RELU, wg, PW4);
             else if (wg < 2 * PW4)
-                p_fwd(lds, g.bs2, nullptr, ct.w1, ct.b1, g.ct_h1, B, O, 0,
+                p_fwd<CLIP>(lds, g.bs2, nullptr, ct.w1, ct.b1, g.ct_h1, B, O, 0,
                       H, ACT_RELU, wg - PW4, PW4);
             else if (wg < 3 * PW4)
-                p_fwd(lds, bs_cur, nullptr, c.w1, c.b1, g.c_h1, B, O, 0, H,
+                p_fwd<CLIP>(lds, bs_cur, nullptr, c.w1, c.b1, g.c_h1, B, O, 0, H,
                       ACT_RELU, wg - 2 * PW4, PW4);
             else
-                p_fwd(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
+                p_fwd<CLIP>(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
                       ACT_RELU, wg - 3 * PW4, PW4);
             p_bar(ctr, tgt); PTIME(g, s, 2);
             // PH2: actor_t.L2 | critic.L2(cat h1, a) | actor.L2
             if (wg < PW3A)
-                p_fwd(lds, g.at_h1, nullptr, at.w2, at.b2, g.at_h2, B, H, 0,
+                p_fwd<CLIP>(lds, g.at_h1, nullptr, at.w2, at.b2, g.at_h2, B, H, 0,
                       H, ACT_NONE, wg, PW3A);
             else if (wg < 2 * PW3A)
-                p_fwd(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A, H,
+                p_fwd<CLIP>(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A, H,
                       ACT_RELU, wg - PW3A, PW3A);
             else
-                p_fwd(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
+                p_fwd<CLIP>(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
                       H, ACT_NONE, wg - 2 * PW3A, PW3B);
             p_bar(ctr, tgt); PTIME(g, s, 3);
             // PH3: L3s
             if (wg < PW3A)
-                p_fwd(lds, g.at_h2, nullptr, at.w3, at.b3, g.at_h3, B, H, 0,
+                p_fwd<CLIP>(lds, g.at_h2, nullptr, at.w3, at.b3, g.at_h3, B, H, 0,
                       H, ACT_RELU, wg, PW3A);
             else if (wg < 2 * PW3A)
-                p_fwd(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H, 0, H,
+                p_fwd<CLIP>(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H, 0, H,
                       ACT_RELU, wg - PW3A, PW3A);
             else
-                p_fwd(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
+                p_fwd<CLIP>(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
                       H, ACT_RELU, wg - 2 * PW3A, PW3B);
             p_bar(ctr, tgt); PTIME(g, s, 4);
             // PH4: heads — actor_t tanh -> a2 | critic softmax -> q |
             //      actor tanh -> a_out
             if (wg < PW3A)
-                p_fwd(lds, g.at_h3, nullptr, at.w4, at.b4, g.a2, B, H, 0, A,
+                p_fwd<CLIP>(lds, g.at_h3, nullptr, at.w4, at.b4, g.a2, B, H, 0, A,
                       ACT_TANH, wg, PW3A);
             else if (wg < 2 * PW3A)
-                p_fwd(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0, K,
+                p_fwd<CLIP>(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0, K,
                       ACT_SOFTMAX, wg - PW3A, PW3A);
             else
-                p_fwd(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
+                p_fwd<CLIP>(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
                       A, ACT_TANH, wg - 2 * PW3A, PW3B);
             // per-step loss accumulators zeroed here (grid barrier below
             // orders this before the quad-chained proj-CE / pgrad adds);
@@ -821,16 +861,16 @@ k_step_persistent(StepArgs g, int nsteps) {
             int q = wg >> 2, m = wg & 3;
             unsigned long long* qc = ctr + 192 + (q << 4);
             if (pipe && wg >= QW && wg < QW + 32) {
-                p_fwd(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
+                p_fwd<CLIP>(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
                       ACT_RELU, wg - QW, 32);
                 t_bar(ctr + 1280, trnd, 32);
-                p_fwd(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
+                p_fwd<CLIP>(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
                       H, ACT_NONE, wg - QW, 32);
                 t_bar(ctr + 1280, trnd, 32);
-                p_fwd(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
+                p_fwd<CLIP>(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
                       H, ACT_RELU, wg - QW, 32);
                 t_bar(ctr + 1280, trnd, 32);
-                p_fwd(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
+                p_fwd<CLIP>(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
                       A, ACT_TANH, wg - QW, 32);
                 PTIMEW(g, s, 53, QW);        // actor crew's end
             }
@@ -838,26 +878,26 @@ k_step_persistent(StepArgs g, int nsteps) {
                 long r0 = (long)rg * 4;
                 int nb = min(4, B - (int)r0);
                 if (pipe) {
-                    p_fwd(lds, g.bs2 + r0 * O, nullptr, at.w1, at.b1,
+                    p_fwd<CLIP>(lds, g.bs2 + r0 * O, nullptr, at.w1, at.b1,
                           g.at_h1 + r0 * H, nb, O, 0, H, ACT_RELU, m, 4);
                     q_bar(qc, qrnd);
-                    p_fwd(lds, g.at_h1 + r0 * H, nullptr, at.w2, at.b2,
+                    p_fwd<CLIP>(lds, g.at_h1 + r0 * H, nullptr, at.w2, at.b2,
                           g.at_h2 + r0 * H, nb, H, 0, H, ACT_NONE, m, 4);
                     q_bar(qc, qrnd);
-                    p_fwd(lds, g.at_h2 + r0 * H, nullptr, at.w3, at.b3,
+                    p_fwd<CLIP>(lds, g.at_h2 + r0 * H, nullptr, at.w3, at.b3,
                           g.at_h3 + r0 * H, nb, H, 0, H, ACT_RELU, m, 4);
                     q_bar(qc, qrnd);
-                    p_fwd(lds, g.at_h3 + r0 * H, nullptr, at.w4, at.b4,
+                    p_fwd<CLIP>(lds, g.at_h3 + r0 * H, nullptr, at.w4, at.b4,
                           g.a2 + r0 * A, nb, H, 0, A, ACT_TANH, m, 4);
                     q_bar(qc, qrnd); PTIME(g, s, 54);
                 }
-                p_fwd(lds, g.ct_h1 + r0 * H, g.a2 + r0 * A, ct.w2, ct.b2,
+                p_fwd<CLIP>(lds, g.ct_h1 + r0 * H, g.a2 + r0 * A, ct.w2, ct.b2,
                       g.ct_h2 + r0 * H, nb, H, A, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd);
-                p_fwd(lds, g.ct_h2 + r0 * H, nullptr, ct.w3, ct.b3,
+                p_fwd<CLIP>(lds, g.ct_h2 + r0 * H, nullptr, ct.w3, ct.b3,
                       g.ct_h3 + r0 * H, nb, H, 0, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd);
-                p_fwd(lds, g.ct_h3 + r0 * H, nullptr, ct.w4, ct.b4,
+                p_fwd<CLIP>(lds, g.ct_h3 + r0 * H, nullptr, ct.w4, ct.b4,
                       g.p_t + r0 * K, nb, H, 0, K, ACT_SOFTMAX, m, 4);
                 if (m == 0)
                     p_project_ce(g, lds, (int)r0);
@@ -896,25 +936,32 @@ k_step_persistent(StepArgs g, int nsteps) {
         PTIME(g, s, 10); PTIME(g, s, 11); PTIME(g, s, 12);
         // PH13: critic dW, 4 jobs split by tile count (l1 is the biggest)
         if (wg < PNWG / 16)
-            p_dw2(lds, g.d1, bs_cur, nullptr, g.g_critic + g.cl[0].w_off,
+            p_dw2<CLIP>(lds, g.d1, bs_cur, nullptr, g.g_critic + g.cl[0].w_off,
                  g.g_critic + g.cl[0].b_off, B, O, 0, H, wg, PNWG / 16);
         else if (wg < PNWG / 2)
-            p_dw2(lds, g.d2, g.c_h1, g.ba, g.g_critic + g.cl[1].w_off,
+            p_dw2<CLIP>(lds, g.d2, g.c_h1, g.ba, g.g_critic + g.cl[1].w_off,
                  g.g_critic + g.cl[1].b_off, B, H, A, H, wg - PNWG / 16,
                  PNWG / 2 - PNWG / 16);
         else if (wg < PNWG * 7 / 8)
-            p_dw2(lds, g.d3, g.c_h2, nullptr, g.g_critic + g.cl[2].w_off,
+            p_dw2<CLIP>(lds, g.d3, g.c_h2, nullptr, g.g_critic + g.cl[2].w_off,
                  g.g_critic + g.cl[2].b_off, B, H, 0, H, wg - PNWG / 2,
                  PNWG * 7 / 8 - PNWG / 2);
         else
-            p_dw2(lds, g.dlog, g.c_h3, nullptr, g.g_critic + g.cl[3].w_off,
+            p_dw2<CLIP>(lds, g.dlog, g.c_h3, nullptr, g.g_critic + g.cl[3].w_off,
                  g.g_critic + g.cl[3].b_off, B, H, 0, K, wg - PNWG * 7 / 8,
                  PNWG - PNWG * 7 / 8);
         p_bar(ctr, tgt); PTIME(g, s, 13);
+        // PH13b (clip-on only): |g_critic|^2 by chunks, all workgroups
+        float csc = 1.f;
+        if (CLIP) {
+            p_grad_sumsq(g.g_critic, g.n_critic, g.gn_part_c, lds);
+            p_bar(ctr, tgt); PTIME(g, s, 56);
+            csc = p_grad_scale(g, 0);
+        }
         // PH14: Adam + target soft-update, critic
-        p_adam_lerp(g.p_critic, g.g_critic, g.m_critic, g.v_critic,
-                    g.p_critic_t, g.n_critic, g.lr_critic, g.tau,
-                    tc0 + s);
+        p_adam_lerp<CLIP>(g.p_critic, g.g_critic, g.m_critic, g.v_critic,
+                          g.p_critic_t, g.n_critic, g.lr_critic, g.tau,
+                          tc0 + s, csc);
         p_bar(ctr, tgt); PTIME(g, s, 14);
         // PH15-25 as ONE phase: the whole policy megachain — critic(s,
         // a_out) forward with UPDATED critic params, policy head gradient,
@@ -939,9 +986,9 @@ k_step_persistent(StepArgs g, int nsteps) {
                 if (s + 1 < nsteps) {
                     p_sample(g, QW, ep0 + s + 1, bt0 + s + 1, bs_nxt);
                     t_bar(ctr + 1280, trnd, 32);
-                    p_fwd(lds, g.bs2, nullptr, ct.w1, ct.b1, g.ct_h1, B,
+                    p_fwd<CLIP>(lds, g.bs2, nullptr, ct.w1, ct.b1, g.ct_h1, B,
                           O, 0, H, ACT_RELU, wg - QW, 32);
-                    p_fwd(lds, bs_nxt, nullptr, c.w1, c.b1, g.c_h1, B, O,
+                    p_fwd<CLIP>(lds, bs_nxt, nullptr, c.w1, c.b1, g.c_h1, B, O,
                           0, H, ACT_RELU, wg - QW, 32);
                     // ... and the rest of the NEXT step's critic forward:
                     // the critic's weights have been final since PH14,
@@ -949,13 +996,13 @@ k_step_persistent(StepArgs g, int nsteps) {
                     // this step's last readers of c_h* and q (PH13, the
                     // CE row) are long past
                     t_bar(ctr + 1280, trnd, 32);
-                    p_fwd(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A,
+                    p_fwd<CLIP>(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A,
                           H, ACT_RELU, wg - QW, 32);
                     t_bar(ctr + 1280, trnd, 32);
-                    p_fwd(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H,
+                    p_fwd<CLIP>(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H,
                           0, H, ACT_RELU, wg - QW, 32);
                     t_bar(ctr + 1280, trnd, 32);
-                    p_fwd(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0,
+                    p_fwd<CLIP>(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0,
                           K, ACT_SOFTMAX, wg - QW, 32);
                 }
                 PTIMEW(g, s, 52, QW);        // tail crew's end
@@ -964,16 +1011,16 @@ k_step_persistent(StepArgs g, int nsteps) {
                 long r0 = (long)rg * 4;
                 int nb = min(4, B - (int)r0);
                 PTIME(g, s, 40);
-                p_fwd(lds, bs_cur + r0 * O, nullptr, c.w1, c.b1,
+                p_fwd<CLIP>(lds, bs_cur + r0 * O, nullptr, c.w1, c.b1,
                       g.pc_h1 + r0 * H, nb, O, 0, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd); PTIME(g, s, 41);
-                p_fwd(lds, g.pc_h1 + r0 * H, g.a_out + r0 * A, c.w2, c.b2,
+                p_fwd<CLIP>(lds, g.pc_h1 + r0 * H, g.a_out + r0 * A, c.w2, c.b2,
                       g.pc_h2 + r0 * H, nb, H, A, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd); PTIME(g, s, 42);
-                p_fwd(lds, g.pc_h2 + r0 * H, nullptr, c.w3, c.b3,
+                p_fwd<CLIP>(lds, g.pc_h2 + r0 * H, nullptr, c.w3, c.b3,
                       g.pc_h3 + r0 * H, nb, H, 0, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd); PTIME(g, s, 43);
-                p_fwd(lds, g.pc_h3 + r0 * H, nullptr, c.w4, c.b4,
+                p_fwd<CLIP>(lds, g.pc_h3 + r0 * H, nullptr, c.w4, c.b4,
                       g.pq + r0 * K, nb, H, 0, K, ACT_SOFTMAX, m, 4);
                 if (m == 0)
                     p_policy_grad(g, (int)r0);
@@ -1010,32 +1057,39 @@ k_step_persistent(StepArgs g, int nsteps) {
         // phase; the counter tick moves to the final phase so both Adams
         // still read this step's t)
         if (wg < PNWG / 16)
-            p_dw2(lds, g.az1, bs_cur, nullptr, g.g_actor + g.al[0].w_off,
+            p_dw2<CLIP>(lds, g.az1, bs_cur, nullptr, g.g_actor + g.al[0].w_off,
                  g.g_actor + g.al[0].b_off, B, O, 0, H, wg, PNWG / 16);
         else if (wg < PNWG * 15 / 32)
-            p_dw2(lds, g.az2, g.pa_h1, nullptr, g.g_actor + g.al[1].w_off,
+            p_dw2<CLIP>(lds, g.az2, g.pa_h1, nullptr, g.g_actor + g.al[1].w_off,
                  g.g_actor + g.al[1].b_off, B, H, 0, H, wg - PNWG / 16,
                  PNWG * 15 / 32 - PNWG / 16);
         else if (wg < PNWG * 7 / 8)
-            p_dw2(lds, g.az3, g.pa_h2, nullptr, g.g_actor + g.al[2].w_off,
+            p_dw2<CLIP>(lds, g.az3, g.pa_h2, nullptr, g.g_actor + g.al[2].w_off,
                  g.g_actor + g.al[2].b_off, B, H, 0, H, wg - PNWG * 15 / 32,
                  PNWG * 7 / 8 - PNWG * 15 / 32);
         else if (wg < PNWG - 2)
-            p_dw2(lds, g.adz, g.pa_h3, nullptr, g.g_actor + g.al[3].w_off,
+            p_dw2<CLIP>(lds, g.adz, g.pa_h3, nullptr, g.g_actor + g.al[3].w_off,
                  g.g_actor + g.al[3].b_off, B, H, 0, A, wg - PNWG * 7 / 8,
                  PNWG - 2 - PNWG * 7 / 8);
         else if (!otail && wg == PNWG - 1)
             p_per_update(g, PNWG - 1);   // PH10-12 did it when otail
         p_bar(ctr, tgt); PTIME(g, s, 26);
+        // PH26b (clip-on only): |g_actor|^2 by chunks.  ALL workgroups take
+        // the phase and its barrier, the ones that sample in PH27 included
+        if (CLIP) {
+            p_grad_sumsq(g.g_actor, g.n_actor, g.gn_part_a, lds);
+            p_bar(ctr, tgt); PTIME(g, s, 57);
+        }
         // PH27: Adam + soft-update, actor (wgs 0-47) overlapped with the
         // NEXT step's PER sample + gather (wgs 48-63; tree was repaired in
         // PH26, schedule counters offset by the pending tick)
         {
             int anw = otail ? PNWG : PNWG * 3 / 4;
             if (wg < anw)
-                p_adam_lerp(g.p_actor, g.g_actor, g.m_actor, g.v_actor,
-                            g.p_actor_t, g.n_actor, g.lr_actor, g.tau,
-                            ta0 + s, anw);
+                p_adam_lerp<CLIP>(g.p_actor, g.g_actor, g.m_actor,
+                                  g.v_actor, g.p_actor_t, g.n_actor,
+                                  g.lr_actor, g.tau, ta0 + s,
+                                  CLIP ? p_grad_scale(g, 1) : 1.f, anw);
             else if (s + 1 < nsteps && B <= (PNWG - PNWG * 3 / 4) * 4)
                 p_sample(g, PNWG * 3 / 4, ep0 + s + 1, bt0 + s + 1, bs_nxt);
             // the next step is pipelined and has no PH4: zero its loss

@@ -338,4 +338,64 @@ __device__ __forceinline__ AdamBias adam_bias(float b1, float b2,
     return {1.f - __powf(b1, (float)t), 1.f - __powf(b2, (float)t)};
 }
 
+// ---- global-norm gradient clipping ------------------------------------------
+// The rule of torch.nn.utils.clip_grad_norm_, per net: norm = sqrt(sum g^2)
+// over the whole gradient slab, scale = min(1, max_norm / (norm + 1e-6)), and
+// Adam consumes scale * g (the slab itself stays raw).  The sum is taken in
+// double, in one fixed order, by the two helpers below; every path calls them
+// over the same chunking, so norm and scale are bitwise equal on all of them.
+// No atomics, no float accumulation.
+#define GN_CHUNK 4096
+
+__host__ __device__ inline int gn_chunks(long n) {
+    return (int)((n + GN_CHUNK - 1) / GN_CHUNK);
+}
+
+// Workgroup-wide (256 threads): the sum of squares of chunk `chunk` of the
+// slab g[0..n) into gn_part[chunk].  Thread t folds elements t, t + 256, ...
+// of the chunk ascending as double(g) * double(g) (exact: 48 bits), then a
+// fixed-order LDS tree folds the 256 partials.  red: 256 doubles of LDS.
+// Ends on a barrier, so red may be reused at once.
+__device__ __forceinline__ void grad_sumsq_chunk(const float* g, long n,
+                                                 int chunk, double* gn_part,
+                                                 double* red) {
+    int tid = threadIdx.x;
+    long lo = (long)chunk * GN_CHUNK;
+    long hi = lo + GN_CHUNK < n ? lo + GN_CHUNK : n;
+    double acc = 0.0;
+    for (long i = lo + tid; i < hi; i += 256) {
+        double x = (double)g[i];
+        acc += x * x;
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) gn_part[chunk] = red[0];
+    __syncthreads();
+}
+
+// The finish, by any one thread (or by many, each for itself): the partials
+// summed in ascending chunk order, the norm and the scale Adam multiplies by.
+struct GradClip { double norm; float scale; };
+
+__device__ __forceinline__ GradClip grad_clip_finish(const double* gn_part,
+                                                     long n,
+                                                     double max_norm) {
+    double sum = 0.0;
+    int nc = gn_chunks(n);
+    for (int c = 0; c < nc; ++c) sum += gn_part[c];
+    double norm = sqrt(sum);
+    return {norm, (float)fmin(1.0, max_norm / (norm + 1e-6))};
+}
+
+// Record one net's norm and scale in the statistics block (one thread).
+__device__ __forceinline__ void grad_stats_write(GradStats* st, int is_actor,
+                                                 GradClip c) {
+    if (is_actor) { st->norm_actor = c.norm; st->scale_actor = c.scale; }
+    else          { st->norm_critic = c.norm; st->scale_critic = c.scale; }
+}
+
 }  // namespace d4pg

@@ -26,7 +26,8 @@ static int64_t create(int64_t obs, int64_t act, int64_t hidden, int64_t atoms,
                       double lr_actor, double lr_critic, double per_alpha,
                       double per_beta0, int64_t per_beta_iters,
                       double per_eps, int64_t seed, bool is_weighting,
-                      bool prioritized, bool true_td, bool gemm_bf16) {
+                      bool prioritized, bool true_td, bool gemm_bf16,
+                      double max_grad_norm) {
     EngineCfg c{};
     c.obs = (int)obs; c.act = (int)act; c.hidden = (int)hidden;
     c.atoms = (int)atoms; c.batch = (int)batch;
@@ -39,6 +40,7 @@ static int64_t create(int64_t obs, int64_t act, int64_t hidden, int64_t atoms,
     c.seed = (uint64_t)seed; c.is_weighting = is_weighting ? 1 : 0;
     c.prioritized = prioritized ? 1 : 0; c.true_td = true_td ? 1 : 0;
     c.gemm_bf16 = gemm_bf16 ? 1 : 0;
+    c.max_grad_norm = max_grad_norm;    // the engine refuses < 0 and NaN
     int64_t h = g_next++;
     g_engines[h] = std::make_unique<Engine>(c);
     return h;
@@ -55,6 +57,7 @@ static py::dict info(int64_t h) {
     d["prioritized"] = e.cfg.prioritized != 0;
     d["true_td"] = e.cfg.true_td != 0;
     d["gemm_precision"] = e.cfg.gemm_bf16 ? "bf16" : "fp32";
+    d["max_grad_norm"] = e.cfg.max_grad_norm;
     d["persistent"] = e.step_path() == Engine::PATH_PERSISTENT;
     d["seed"] = (int64_t)e.cfg.seed;
     // episodes one collection window can hold; 0 before collect_alloc
@@ -276,6 +279,18 @@ static py::dict counters(int64_t h) {
     d["max_priority"] = c.max_priority;
     d["loss_critic"] = c.loss_critic;
     d["loss_actor"] = c.loss_actor;
+    return d;
+}
+
+// gradient-clip statistics of the last step (zeros with clipping off): one
+// small device-to-host copy, no launch
+static py::dict grad_stats(int64_t h) {
+    GradStats g = get(h).read_grad_stats();
+    py::dict d;
+    d["norm_actor"] = g.norm_actor;
+    d["norm_critic"] = g.norm_critic;
+    d["scale_actor"] = g.scale_actor;
+    d["scale_critic"] = g.scale_critic;
     return d;
 }
 
@@ -642,6 +657,11 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
         {"tstamp", {e.ws.tstamp, {64}, true, false}},
         {"sum_tree", {e.ws.sum_tree, {2 * e.ws.tree_cap}, false, true}},
         {"min_tree", {e.ws.min_tree, {2 * e.ws.tree_cap}, false, true}},
+        // per-chunk sums of squares of the gradient slabs (clipping on)
+        {"gn_part_actor",
+         {e.ws.gn_part_a, {gn_chunks(e.anet.n_params)}, false, true}},
+        {"gn_part_critic",
+         {e.ws.gn_part_c, {gn_chunks(e.cnet.n_params)}, false, true}},
     };
     if (e.stage_pool_) {
         // the actor snapshot and the staging store of an overlapped
@@ -684,7 +704,7 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
 }  // namespace d4pg
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
-    // gemm_bf16 is the one trailing argument with a default
+    // gemm_bf16 and max_grad_norm are the trailing arguments with defaults
     mod.def("create", &d4pg::create,
             py::arg("obs"), py::arg("act"), py::arg("hidden"),
             py::arg("atoms"), py::arg("batch"), py::arg("capacity"),
@@ -694,7 +714,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("per_beta_iters"), py::arg("per_eps"), py::arg("seed"),
             py::arg("is_weighting"), py::arg("prioritized"),
             py::arg("true_td"),
-            py::arg("gemm_bf16") = false);
+            py::arg("gemm_bf16") = false,
+            py::arg("max_grad_norm") = 0.0);
     mod.def("destroy", &d4pg::destroy);
     mod.def("info", &d4pg::info);
     mod.def("load_slab", &d4pg::load_slab);
@@ -713,6 +734,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("replay_async", &d4pg::replay_async);
     mod.def("sync", &d4pg::sync);
     mod.def("counters", &d4pg::counters);
+    mod.def("grad_stats", &d4pg::grad_stats);
     mod.def("rollout_alloc", &d4pg::rollout_alloc);
     mod.def("rollout_run", &d4pg::rollout_run);
     mod.def("rollout_set_state", &d4pg::rollout_set_state);

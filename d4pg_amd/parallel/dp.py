@@ -88,7 +88,12 @@ class _SlabComm:
 
 class DPEngine:
     """Synchronous gradient-DP wrapper around a FusedEngine (see module
-    docstring).  train_steps(n) == n data-parallel train steps."""
+    docstring).  train_steps(n) == n data-parallel train steps.
+
+    Gradient clipping (an engine built with max_grad_norm > 0) needs nothing
+    here: the engine takes each net's norm at the head of its APPLY phase,
+    that is AFTER the all-reduce below, so every rank clips by the norm of
+    the averaged gradient and applies the same scale."""
 
     def __init__(self, engine: FusedEngine, group=None):
         self.engine = engine

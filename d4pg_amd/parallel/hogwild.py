@@ -33,6 +33,7 @@ def _build_agent(args, env, seed):
                 critic_dist_info=critic_dist_info(args),
                 n_steps=args.n_steps, seed=seed,
                 gemm_precision=getattr(args, "gemm_precision", "fp32"),
+                max_grad_norm=getattr(args, "clip_grad_norm", 0.0),
                 **noise_kwargs(args))
 
 

@@ -174,6 +174,8 @@ class DistributedD4PG:
             # a learner-side option: actor and evaluator ranks only act
             gemm_precision=(getattr(args, "gemm_precision", "fp32")
                             if self.is_learner else "fp32"),
+            max_grad_norm=(getattr(args, "clip_grad_norm", 0.0)
+                           if self.is_learner else 0.0),
             **noise_kwargs(args))
         self.rng = np.random.default_rng(seed)
 

@@ -185,6 +185,19 @@ class Worker:
             if global_count is not None:
                 global_count += 1     # HogWild-tolerated non-atomic increment
 
+    def grad_norm_scalars(self):
+        """With --clip_grad_norm > 0 on the hip backend: the gradient norms
+        of the cycle's last train step, as (tag, value) pairs (one small
+        device-to-host copy; the cycle's train steps have been synchronised).
+        Empty otherwise, so an unclipped run logs what it always logged."""
+        if float(getattr(self.args, "clip_grad_norm", 0.0)) <= 0.0 \
+                or getattr(self.agent, "backend", "eager") != "hip" \
+                or self.agent.engine is None:
+            return []
+        st = self.agent.engine.engine.grad_stats()
+        return [("grad_norm_actor", float(st["norm_actor"])),
+                ("grad_norm_critic", float(st["norm_critic"]))]
+
     def evaluate(self):
         if self._device_kind is not None:
             # eval_trials greedy device envs on the slab the step updates:
@@ -227,6 +240,8 @@ class Worker:
                                            self.grad_meter.rate(), step)
                     self.writer.add_scalar("env_steps_per_sec",
                                            self.env_meter.rate(), step)
+                    for tag, val in self.grad_norm_scalars():
+                        self.writer.add_scalar(tag, val, step)
                 if self.args.debug:
                     print(f"[worker {self.name}] epoch {epoch} step {step} "
                           f"avg_test_reward {avg_r:.2f} success {succ:.2f}",

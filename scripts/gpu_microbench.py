@@ -47,13 +47,14 @@ def bench_eager_gpu(steps):
 
 
 def make_engine(batch=64, hidden=256, obs=3, act=1, cap=1000000,
-                gemm_precision="fp32"):
+                gemm_precision="fp32", max_grad_norm=0.0):
     from d4pg_amd.ops import FusedEngine
     from d4pg_amd.models import actor, critic
     eng = FusedEngine(obs_dim=obs, act_dim=act, hidden=hidden, n_atoms=51,
                       batch=batch, capacity=cap, v_min=-300.0, v_max=0.0,
                       gamma_n=0.99 ** 5, tau=0.001, lr_actor=1e-4,
-                      lr_critic=1e-4, seed=0, gemm_precision=gemm_precision)
+                      lr_critic=1e-4, seed=0, gemm_precision=gemm_precision,
+                      max_grad_norm=max_grad_norm)
     torch.manual_seed(0)
     a = actor(obs, act, hidden=hidden)
     c = critic(obs, act, {"type": "categorical", "v_min": -300.0,

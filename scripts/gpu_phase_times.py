@@ -5,7 +5,10 @@ The kernel stamps step 1 of a multi-step launch: the first step that runs
 the steady-state schedule (the tail crew's precompute under the previous
 policy block, the merged forward phase).  Step 0 of a launch runs the
 un-pipelined PH0-PH4 schedule instead; `--first` stamps that one through
-one-step launches.
+one-step launches.  `--clip C` builds the engine with max_grad_norm=C (the
+clip-on kernel; 1e30 keeps the work and never binds): its two extra phases,
+the chunked |g|^2 plus the grid barrier that publishes it, are stamped in
+slots 56 / 57 and sit inside the "c.adam" and "a.adam" rows.
 """
 
 import os
@@ -37,6 +40,8 @@ INNER = [
     ("fwd: actor crew end", 53, 5),
     ("policy: quad 0 end", 51, 14),
     ("policy: tail crew end", 52, 14),
+    ("clip: critic |g|^2 + barrier", 56, 13),
+    ("clip: actor |g|^2 + barrier", 57, 26),
 ]
 
 # quad 0's walk through the policy megachain: each slot is one layer tile
@@ -49,7 +54,10 @@ POLICY_SLOTS = [
 ]
 
 first = "--first" in sys.argv[1:]
-eng = make_engine()
+clip = 0.0
+if "--clip" in sys.argv[1:]:
+    clip = float(sys.argv[sys.argv.index("--clip") + 1])
+eng = make_engine(max_grad_norm=clip)
 eng.step(50)          # warm; stamps overwritten each launch
 if first:
     eng.step(1)

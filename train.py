@@ -49,6 +49,7 @@ def main(argv=None):
                  critic_dist_info=critic_dist_info(args),
                  n_steps=args.n_steps, device=device, backend=backend,
                  seed=args.seed, gemm_precision=args.gemm_precision,
+                 max_grad_norm=args.clip_grad_norm,
                  **noise_kwargs(args))
     rd = run_dir_name(args)
     writer = SummaryWriter(rd)
