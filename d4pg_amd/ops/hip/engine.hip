@@ -36,6 +36,7 @@
 #include "engine_synth.hip"
 #include "engine_eval.hip"
 #include "engine_stage.hip"
+#include "engine_mfma_tile.hip"
 #include "engine_mfma.hip"
 #include "engine_mfma_bf16.hip"
 #include "engine_persistent.hip"
@@ -285,19 +286,15 @@ public:
         ws.az2 = carve<float>((long)B * H, off);
         ws.az3 = carve<float>((long)B * H, off);
         // split-K disjoint partials: the wide step's dW (max over layers of
-        // ksplit * (weights + bias); the ksplit formula mirrors
-        // launch_bwd's) and the MFMA heads' forward partials, which
-        // actor_forward already needs at B = 512 where the step itself is
-        // still row-block.  Segments past the last batch chunk are empty
+        // ksplit * (weights + bias)) and the MFMA heads' forward partials,
+        // which actor_forward already needs at B = 512 where the step itself
+        // is still row-block.  Segments past the last batch chunk are empty
         // when B is no power-of-two multiple of MT_K; k_mfma_dw zero-fills
         // them
         long dwp = 0;
         if (fwd_uses_mfma(B)) {
             auto dw_need = [&](int in_n, int out) {
-                int ntm = ceil_div(in_n, MT_M), ntn = ceil_div(out, MT_N);
-                int ks = 1;
-                while (ntm * ntn * ks < 256 && ks * 2 * MT_K <= B) ks *= 2;
-                long v = (long)ks * ((long)in_n * out + out);
+                long v = (long)dw_ksplit(in_n, out) * ((long)in_n * out + out);
                 if (v > dwp) dwp = v;
             };
             auto need = [&](const LayerDesc& l) {
@@ -305,11 +302,8 @@ public:
                 dw_need(l.in1, l.out);
                 if (l.in2 > 0) dw_need(l.in2, l.out);
                 if (l.out <= 64) {      // split-K head fwd partials
-                    int it = l.in1 + l.in2;
-                    int ntmh = ceil_div(B, MT_M), ksh = 1;
-                    while (ntmh * ksh < 512 && ksh * 2 * MT_K <= it)
-                        ksh *= 2;
-                    long v2 = (long)ksh * (long)B * l.out;
+                    long v2 = (long)head_ksplit(B, l.in1 + l.in2) * (long)B *
+                              l.out;
                     if (v2 > dwp) dwp = v2;
                 }
             };
@@ -378,6 +372,23 @@ public:
     // (the train step has its own split, see step_path()).
     static bool fwd_uses_mfma(int rows) { return rows >= 512; }
 
+    // The split-K factors, for layout() (which sizes dw_parts by them) and
+    // the launchers alike: double until the grid covers the chip, as long
+    // as K still holds one f32 chunk (MT_K) per segment.  The bf16 kernels
+    // take the same factors.
+    // dW of one [in_n][out] block, K = the batch:
+    int dw_ksplit(int in_n, int out) const {
+        int nt = ceil_div(in_n, MT_M) * ceil_div(out, MT_N), ks = 1;
+        while (nt * ks < 256 && ks * 2 * MT_K <= cfg.batch) ks *= 2;
+        return ks;
+    }
+    // forward of a narrow head (out <= 64: one column tile), K = in_total:
+    static int head_ksplit(int rows, int in_total) {
+        int ntm = ceil_div(rows, MT_M), ks = 1;
+        while (ntm * ks < 512 && ks * 2 * MT_K <= in_total) ks *= 2;
+        return ks;
+    }
+
     // (the launchers the rollout uses take their stream; the train step's
     // run on the engine's)
     void launch_fwd_valu(const FwdJob& j, hipStream_t st) {
@@ -404,8 +415,7 @@ public:
     // launch was chip-starved on both the VALU kernel (~60 us) and MFMA.
     void launch_fwd_mfma_head(const FwdJob& j, bool bf16 = false) {
         int ntm = ceil_div(j.B, MT_M);
-        int ks = 1;
-        while (ntm * ks < 512 && ks * 2 * MT_K <= j.in1 + j.in2) ks *= 2;
+        int ks = head_ksplit(j.B, j.in1 + j.in2);
         hipLaunchKernelGGL(bf16 ? k_mfma_fwd_bf16 : k_mfma_fwd,
                            dim3(ntm * ks), dim3(256), 0, stream,
                            j.x1, j.x2, j.wt, j.bias, j.y, j.B, j.in1, j.in2,
@@ -454,10 +464,7 @@ public:
                                float* db) {
                 int ntm = ceil_div(in_n, MT_M);
                 int ntn = ceil_div(l.out, MT_N);
-                int ksplit = 1;
-                while (ntm * ntn * ksplit < 256 &&
-                       ksplit * 2 * MT_K <= cfg.batch)
-                    ksplit *= 2;
+                int ksplit = dw_ksplit(in_n, l.out);
                 hipLaunchKernelGGL(k_dw, dim3(ntm * ntn * ksplit),
                                    dim3(256), 0, stream, dz, xop,
                                    (const float*)nullptr, dwt, db,

@@ -8,7 +8,8 @@
 // accumulates in fp32.  Everything after the accumulator — split-K `parts`,
 // bias, activation, ReLU mask, k_dw_reduce, k_head_finish — is the fp32 code
 // of the f32 kernels: the C/D lane map of 32x32x16_bf16 equals that of
-// 32x32x2_f32, so the epilogues are the same text.  db is the fp32 column
+// 32x32x2_f32, so both call the one set of epilogues in
+// engine_mfma_tile.hip.  db is the fp32 column
 // sum of the bf16-rounded dz fragments the dW MFMAs consumed.  No atomics.
 //
 // Tile: the f32 kernels' 64x128 workgroup tile and 2x2 wave split (each wave
@@ -112,9 +113,9 @@ __device__ __forceinline__ void bf16_pipeline(FL ld, FW wr, int nch, bool bias,
                                               f32x16& a00, f32x16& a01,
                                               float& bias0, float& bias1) {
     if (nch <= 0) return;               // block-uniform: empty K segment
-    int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    int wm0 = (wid >> 1) * 32, wn0 = (wid & 1) * 64;
-    int r = lane & 31, kh = (lane >> 5) * 8;
+    WavePos w;
+    const int wm0 = w.wm0, wn0 = w.wn0;
+    int r = w.lane & 31, kh = (w.lane >> 5) * 8;
     ld(0);
     wr(0);
     __syncthreads();
@@ -155,17 +156,9 @@ k_mfma_fwd_bf16(const float* __restrict__ x1, const float* __restrict__ x2,
                 int act_kind, int ksplit, float* __restrict__ parts) {
     BF16_LDS_DECL;
     int in_total = in1 + in2;
-    int ntn = (out + MT_N - 1) / MT_N;
-    int ntm = (B + MT_M - 1) / MT_M;
-    int seg = blockIdx.x / (ntm * ntn);
-    int tile = blockIdx.x % (ntm * ntn);
-    int m0 = (tile / ntn) * MT_M, n0 = (tile % ntn) * MT_N;
-    int nch_total = (in_total + BT_K - 1) / BT_K;
-    int nch_seg = (nch_total + ksplit - 1) / ksplit;
-    int ch0 = seg * nch_seg;
-    int nch = min(nch_seg, nch_total - ch0);
-    int kbase = ch0 * BT_K;
-    int tid = threadIdx.x, lane = tid & 63;
+    const MfmaTile t = mfma_tile(B, out, in_total, BT_K, ksplit);
+    const int m0 = t.m0, n0 = t.n0, kbase = t.ch0 * BT_K;
+    int tid = threadIdx.x;
     f32x16 acc00 = {}, acc01 = {};
     // A = X, k-fastest: rows m0 + tid/16 + 16u, k (tid%16)*4 .. +3
     // B = Wt, column-fastest: columns n0 + (tid%32)*4 .. +3, k (tid/32)*8 + u
@@ -173,83 +166,24 @@ k_mfma_fwd_bf16(const float* __restrict__ x1, const float* __restrict__ x2,
     const int brq = (tid & 31) * 4, bkg = (tid >> 5) * 8;
     const bool vecA = (in1 % 4 == 0) && (m0 + MT_M <= B) && aligned16(x1);
     const bool vecB = (out % 4 == 0) && (n0 + MT_N <= out) && aligned16(wt);
+    const GuardedCat X{x1, x2, B, in1, in2};
+    const GuardedMat W{wt, in_total, out};
     float ta[16], tb[32];
     auto ld = [&](int k0r) {
         int k0 = kbase + k0r;
-        if (vecA && k0 + BT_K <= in1) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                float4 v = *reinterpret_cast<const float4*>(
-                    x1 + (long)(m0 + arq + 16 * u) * in1 + k0 + akq);
-                ta[4 * u] = v.x; ta[4 * u + 1] = v.y;
-                ta[4 * u + 2] = v.z; ta[4 * u + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                int gm = m0 + arq + 16 * u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    int gk = k0 + akq + c;
-                    float v = 0.f;
-                    if (gm < B && gk < in_total)
-                        v = (gk < in1) ? x1[(long)gm * in1 + gk]
-                                       : x2[(long)gm * in2 + (gk - in1)];
-                    ta[4 * u + c] = v;
-                }
-            }
-        }
-        if (vecB && k0 + BT_K <= in_total) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                float4 v = *reinterpret_cast<const float4*>(
-                    wt + (long)(k0 + bkg + u) * out + n0 + brq);
-                tb[4 * u] = v.x; tb[4 * u + 1] = v.y;
-                tb[4 * u + 2] = v.z; tb[4 * u + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                int gk = k0 + bkg + u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    int gn = n0 + brq + c;
-                    tb[4 * u + c] = (gk < in_total && gn < out)
-                        ? wt[(long)gk * out + gn] : 0.f;
-                }
-            }
-        }
+        mfma_stage<4>(ta, vecA && k0 + BT_K <= in1, X, [&](int u) {
+            return RunPos{m0 + arq + 16 * u, k0 + akq}; });
+        mfma_stage<8>(tb, vecB && k0 + BT_K <= in_total, W, [&](int u) {
+            return RunPos{k0 + bkg + u, n0 + brq}; });
     };
     auto wr = [&](int buf) {
         bf16_wr_kf<MT_M>(As2[buf], ta, tid);
         bf16_wr_rf128(Bs2[buf], tb, tid);
     };
     float nb0 = 0.f, nb1 = 0.f;
-    bf16_pipeline(ld, wr, nch, false, As2, Bs2, acc00, acc01, nb0, nb1);
-    int wid = tid >> 6;
-    int wm0 = (wid >> 1) * 32, wn0 = (wid & 1) * 64;
-    const f32x16* accs[2] = {&acc00, &acc01};
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            int row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-            int col = lane & 31;
-            int gm = m0 + wm0 + row;
-            int gn = n0 + wn0 + t * 32 + col;
-            if (gm < B && gn < out) {
-                if (ksplit > 1) {
-                    parts[((long)seg * B + gm) * out + gn] =
-                        (*accs[t])[reg];
-                } else {
-                    float v = (*accs[t])[reg] + bias[gn];
-                    if (act_kind == ACT_RELU) v = fmaxf(v, 0.f);
-                    else if (act_kind == ACT_TANH) v = tanhf(v);
-                    y[(long)gm * out + gn] = v;
-                }
-            }
-        }
-    }
+    bf16_pipeline(ld, wr, t.nch, false, As2, Bs2, acc00, acc01, nb0, nb1);
+    mfma_epilogue_fwd(t, acc00, acc01, bias, y, B, out, act_kind, ksplit,
+                      parts);
 }
 
 // dX[B, in_lo:in_hi] = (bf16(dz[B,out]) @ bf16(Wt)^T) * act'(hprev);
@@ -260,10 +194,9 @@ k_mfma_dx_bf16(const float* __restrict__ dz, const float* __restrict__ wt,
                int B, int in_lo, int in_hi, int out, int prev_act) {
     BF16_LDS_DECL;
     int span = in_hi - in_lo;
-    int ntn = (span + MT_N - 1) / MT_N;
-    int m0 = (blockIdx.x / ntn) * MT_M;
-    int n0 = (blockIdx.x % ntn) * MT_N;             // relative i tile
-    int tid = threadIdx.x, lane = tid & 63;
+    const MfmaTile t = mfma_tile(B, span, out, BT_K, 1, false);
+    const int m0 = t.m0, n0 = t.n0;                 // n0: relative i tile
+    int tid = threadIdx.x;
     f32x16 acc00 = {}, acc01 = {};
     // both operands k(=o)-fastest:
     //   A[m(=b)][k] = dz[b][o], rows m0 + tid/16 + 16u (u < 4)
@@ -272,81 +205,28 @@ k_mfma_dx_bf16(const float* __restrict__ dz, const float* __restrict__ wt,
     const bool vec = (out % 4 == 0) && aligned16(dz) && aligned16(wt);
     const bool vecA = vec && (m0 + MT_M <= B);
     const bool vecB = vec && (n0 + MT_N <= span);
+    const GuardedMat DZ{dz, B, out};
+    const GuardedMat W{wt, in_hi, out};
     float ta[16], tb[32];
     auto ld = [&](int k0) {
         bool full = k0 + BT_K <= out;
-        if (vecA && full) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                float4 v = *reinterpret_cast<const float4*>(
-                    dz + (long)(m0 + rq + 16 * u) * out + k0 + kq);
-                ta[4 * u] = v.x; ta[4 * u + 1] = v.y;
-                ta[4 * u + 2] = v.z; ta[4 * u + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                int gm = m0 + rq + 16 * u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    int gk = k0 + kq + c;
-                    ta[4 * u + c] = (gm < B && gk < out)
-                        ? dz[(long)gm * out + gk] : 0.f;
-                }
-            }
-        }
-        if (vecB && full) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                float4 v = *reinterpret_cast<const float4*>(
-                    wt + (long)(in_lo + n0 + rq + 16 * u) * out + k0 + kq);
-                tb[4 * u] = v.x; tb[4 * u + 1] = v.y;
-                tb[4 * u + 2] = v.z; tb[4 * u + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                int gi = in_lo + n0 + rq + 16 * u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    int gk = k0 + kq + c;
-                    tb[4 * u + c] = (gi < in_hi && gk < out)
-                        ? wt[(long)gi * out + gk] : 0.f;
-                }
-            }
-        }
+        mfma_stage<4>(ta, vecA && full, DZ, [&](int u) {
+            return RunPos{m0 + rq + 16 * u, k0 + kq}; });
+        mfma_stage<8>(tb, vecB && full, W, [&](int u) {
+            return RunPos{in_lo + n0 + rq + 16 * u, k0 + kq}; });
     };
     auto wr = [&](int buf) {
         bf16_wr_kf<MT_M>(As2[buf], ta, tid);
         bf16_wr_kf<MT_N>(Bs2[buf], tb, tid);
     };
     float nb0 = 0.f, nb1 = 0.f;
-    bf16_pipeline(ld, wr, (out + BT_K - 1) / BT_K, false, As2, Bs2, acc00,
-                  acc01, nb0, nb1);
-    int wid = tid >> 6;
-    int wm0 = (wid >> 1) * 32, wn0 = (wid & 1) * 64;
-    const f32x16* accs[2] = {&acc00, &acc01};
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            int row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-            int col = lane & 31;
-            int gm = m0 + wm0 + row;
-            int gn = n0 + wn0 + t * 32 + col;          // relative i
-            if (gm < B && gn < span) {
-                long rel = (long)gm * span + gn;
-                float m_ = hprev ? act_mask(prev_act, hprev[rel]) : 1.f;
-                dx[rel] = (*accs[t])[reg] * m_;
-            }
-        }
-    }
+    bf16_pipeline(ld, wr, t.nch, false, As2, Bs2, acc00, acc01, nb0, nb1);
+    mfma_epilogue_dx(t, acc00, acc01, hprev, dx, B, span, prev_act);
 }
 
 // dWt[in,out] = bf16(X)^T[in,B] @ bf16(dz[B,out]) (K dimension = batch),
 // db[o] = sum_b bf16(dz[b][o]); arguments, grid and split-K `parts` as
-// k_mfma_dw.  A segment past the last batch chunk (nch <= 0) loads nothing
-// and publishes zero partials, which k_dw_reduce needs.
+// k_mfma_dw.
 __global__ void __launch_bounds__(256, 2)
 k_mfma_dw_bf16(const float* __restrict__ dz, const float* __restrict__ x1,
                const float* __restrict__ x2, float* __restrict__ dwt,
@@ -354,18 +234,10 @@ k_mfma_dw_bf16(const float* __restrict__ dz, const float* __restrict__ x1,
                int ksplit, float* __restrict__ parts) {
     BF16_LDS_DECL;
     int in_total = in1 + in2;
-    int ntn = (out + MT_N - 1) / MT_N;
-    int nti = (in_total + MT_M - 1) / MT_M;
-    int seg = blockIdx.x / (nti * ntn);
-    int tile = blockIdx.x % (nti * ntn);
-    int m0 = (tile / ntn) * MT_M;                      // i tile
-    int n0 = (tile % ntn) * MT_N;                      // o tile
-    int nch_total = (B + BT_K - 1) / BT_K;
-    int nch_seg = (nch_total + ksplit - 1) / ksplit;
-    int ch0 = seg * nch_seg;
-    int nch = min(nch_seg, nch_total - ch0);
-    long b_base = (long)ch0 * BT_K;
-    int tid = threadIdx.x, lane = tid & 63;
+    const MfmaTile t = mfma_tile(in_total, out, B, BT_K, ksplit);
+    const int m0 = t.m0, n0 = t.n0;                 // i tile, o tile
+    int b_base = t.ch0 * BT_K;
+    int tid = threadIdx.x;
     f32x16 acc00 = {}, acc01 = {};
     // both operands row-fastest (k = batch row is the slow index in HBM):
     //   A[m(=i)][k(=b)] = x[b][i]: i m0 + (tid%16)*4 .. +3, b (tid/16)*4 + u
@@ -374,100 +246,29 @@ k_mfma_dw_bf16(const float* __restrict__ dz, const float* __restrict__ x1,
     const int brq = (tid & 31) * 4, bkg = (tid >> 5) * 8;
     const bool vecA = (in1 % 4 == 0) && (m0 + MT_M <= in1) && aligned16(x1);
     const bool vecB = (out % 4 == 0) && (n0 + MT_N <= out) && aligned16(dz);
+    const GuardedCat X{x1, x2, B, in1, in2};
+    const GuardedMat DZ{dz, B, out};
     float ta[16], tb[32];
     auto ld = [&](int k0) {
         bool full = b_base + k0 + BT_K <= B;
-        if (vecA && full) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                float4 v = *reinterpret_cast<const float4*>(
-                    x1 + (b_base + k0 + akg + u) * in1 + m0 + arq);
-                ta[4 * u] = v.x; ta[4 * u + 1] = v.y;
-                ta[4 * u + 2] = v.z; ta[4 * u + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                long gb = b_base + k0 + akg + u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    int gi = m0 + arq + c;
-                    float v = 0.f;
-                    if (gb < B && gi < in_total)
-                        v = (gi < in1) ? x1[gb * in1 + gi]
-                                       : x2[gb * in2 + (gi - in1)];
-                    ta[4 * u + c] = v;
-                }
-            }
-        }
-        if (vecB && full) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                float4 v = *reinterpret_cast<const float4*>(
-                    dz + (b_base + k0 + bkg + u) * out + n0 + brq);
-                tb[4 * u] = v.x; tb[4 * u + 1] = v.y;
-                tb[4 * u + 2] = v.z; tb[4 * u + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                long gb = b_base + k0 + bkg + u;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    int go = n0 + brq + c;
-                    tb[4 * u + c] = (gb < B && go < out)
-                        ? dz[gb * out + go] : 0.f;
-                }
-            }
-        }
+        mfma_stage<4>(ta, vecA && full, X, [&](int u) {
+            return RunPos{b_base + k0 + akg + u, m0 + arq}; });
+        mfma_stage<8>(tb, vecB && full, DZ, [&](int u) {
+            return RunPos{b_base + k0 + bkg + u, n0 + brq}; });
     };
     auto wr = [&](int buf) {
         bf16_wr_rf64(As2[buf], ta, tid);
         bf16_wr_rf128(Bs2[buf], tb, tid);
     };
-    int wid = tid >> 6;
-    int wm0 = (wid >> 1) * 32, wn0 = (wid & 1) * 64;
     // db rides the B fragments of the wm0 == 0 waves of the m0 == 0 tiles
     // (wave-uniform choice)
-    const bool want_db = db && wm0 == 0 && m0 == 0;
+    WavePos w;
+    const bool want_db = db && w.wm0 == 0 && m0 == 0;
     float bias0 = 0.f, bias1 = 0.f;
-    bf16_pipeline(ld, wr, nch, want_db, As2, Bs2, acc00, acc01, bias0, bias1);
-    const f32x16* accs[2] = {&acc00, &acc01};
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            int row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-            int col = lane & 31;
-            int gi = m0 + wm0 + row;
-            int go = n0 + wn0 + t * 32 + col;
-            if (gi < in_total && go < out) {
-                if (ksplit > 1)
-                    // disjoint per-segment partials (k_dw_reduce sums)
-                    parts[((long)seg * in_total + gi) * out + go] =
-                        (*accs[t])[reg];
-                else
-                    dwt[(long)gi * out + go] = (*accs[t])[reg];
-            }
-        }
-    }
-    if (want_db) {
-        // combine the two k halves (lane l and l^32 share a column)
-        bias0 += __shfl_xor(bias0, 32, 64);
-        bias1 += __shfl_xor(bias1, 32, 64);
-        int r = lane & 31;
-        if ((lane >> 5) == 0) {
-            int go0 = n0 + wn0 + r, go1 = n0 + wn0 + 32 + r;
-            if (ksplit > 1) {
-                long off = (long)ksplit * in_total * out + (long)seg * out;
-                if (go0 < out) parts[off + go0] = bias0;
-                if (go1 < out) parts[off + go1] = bias1;
-            } else {
-                if (go0 < out) db[go0] = bias0;
-                if (go1 < out) db[go1] = bias1;
-            }
-        }
-    }
+    bf16_pipeline(ld, wr, t.nch, want_db, As2, Bs2, acc00, acc01, bias0,
+                  bias1);
+    mfma_epilogue_dw(t, acc00, acc01, bias0, bias1, want_db, dwt, db,
+                     in_total, out, ksplit, parts);
 }
 
 }  // namespace d4pg

@@ -131,3 +131,27 @@ def test_wide_tree_writeback(wstepped):
     for i in single[:64]:
         assert leaves[i] == pytest.approx(lut[i] ** 0.6, rel=1e-5)
     assert o["counters"]["adam_t_actor"] == 1
+
+
+# ---------------------------------------------------------------------------
+# the f32 MFMA GEMMs one by one (the harness of tests/_wide_gemm.py, which
+# test_gpu_wide_bf16.py runs with bf16 operands): expected = a @ b (+ bias) in
+# float64 from the engine's own fp32 inputs of that GEMM, bound
+# (K + ksplit + 2) * 2^-23 * (|a| @ |b| + |bias|) — any order of fp32
+# accumulation over K terms plus the split-K sum stays inside it.
+# ---------------------------------------------------------------------------
+
+@pytest.fixture(scope="module", params=["a", "b", "c"])
+def phased_fp32(request):
+    from _wide_gemm import run_phased
+    return run_phased(request.param, "fp32")
+
+
+def test_fp32_critic_phase_gemm_by_gemm(phased_fp32):
+    from _wide_gemm import check_critic_phase
+    check_critic_phase(phased_fp32)
+
+
+def test_fp32_actor_phase_gemm_by_gemm(phased_fp32):
+    from _wide_gemm import check_actor_phase
+    check_actor_phase(phased_fp32)

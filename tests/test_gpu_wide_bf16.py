@@ -21,270 +21,32 @@ the bound; outputs behind tanh or softmax use the 5e-5 atol of
 tests/test_gpu_wide.py.
 """
 
-import copy
-
 import numpy as np
 import pytest
 import torch
 
+from _wide_gemm import (CONFIGS, LR, SLABS, Net, _engine, _gemm, _ks_dw,
+                        _modules, _rows, check_actor_phase,
+                        check_critic_phase, run_phased)
+
 pytestmark = pytest.mark.gpu
 
-GAMMA_N = 0.99 ** 5
-TAU, LR = 0.001, 1e-4
-V_MIN, V_MAX = -300.0, 0.0
-N_ROWS = 4096
-U = 2.0 ** -23
-SLABS = ["actor", "actor_target", "critic", "critic_target", "g_actor",
-         "g_critic", "m_actor", "v_actor", "m_critic", "v_critic"]
-
-# a: aligned interior tiles, odd fan-in 17, concat 134, head 51 with split-K
-# b: N edge tile 128+72, K tail of 8, B % 64 = 10, dW K = 650 (empty tail
-#    split-K segments)
-# c: H % 8 != 0, a single M edge tile
-CONFIGS = {
-    "a": dict(O=17, A=6, H=128, K=51, B=1024),
-    "b": dict(O=11, A=3, H=200, K=21, B=650),
-    "c": dict(O=3, A=1, H=100, K=51, B=520),
-}
-
-CRITIC_BUFS = ["bs", "ba", "bs2", "at_h1", "at_h2", "at_h3", "a2", "ct_h1",
-               "ct_h2", "ct_h3", "p_t", "c_h1", "c_h2", "c_h3", "q", "dlog",
-               "d1", "d2", "d3"]
-ACTOR_BUFS = ["bs", "pa_h1", "pa_h2", "pa_h3", "a_out", "pc_h1", "pc_h2",
-              "pc_h3", "pq", "pd3", "pd2", "pdh1", "pda", "adz", "az1", "az2",
-              "az3"]
-
-
-def _dist(c):
-    return {"type": "categorical", "v_min": V_MIN, "v_max": V_MAX,
-            "n_atoms": c["K"]}
-
-
-def _modules(c, seed=5):
-    from d4pg_amd.models import actor, critic
-    torch.manual_seed(seed)
-    a = actor(c["O"], c["A"], hidden=c["H"])
-    cr = critic(c["O"], c["A"], _dist(c), hidden=c["H"])
-    return a, copy.deepcopy(a), cr, copy.deepcopy(cr)
-
-
-def _rows(c, seed=7):
-    rng = np.random.default_rng(seed)
-    n = N_ROWS
-    return (rng.standard_normal((n, c["O"])).astype("f"),
-            rng.uniform(-1, 1, (n, c["A"])).astype("f"),
-            rng.uniform(-30, 0, n).astype("f"),
-            rng.standard_normal((n, c["O"])).astype("f"),
-            (rng.random(n) < 0.05).astype("f"))
-
-
-def _engine(c, precision="bf16", mods=None, rows=None, seed=11, batch=None):
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=c["O"], act_dim=c["A"], hidden=c["H"],
-                      n_atoms=c["K"], batch=batch or c["B"], capacity=8192,
-                      v_min=V_MIN, v_max=V_MAX, gamma_n=GAMMA_N, tau=TAU,
-                      lr_actor=LR, lr_critic=LR, seed=seed,
-                      gemm_precision=precision)
-    eng.load_from_modules(*(mods or _modules(c)))
-    eng.ingest(*[torch.from_numpy(x) for x in (rows or _rows(c))])
-    return eng
-
 
 # ---------------------------------------------------------------------------
-# the oracle
-# ---------------------------------------------------------------------------
-
-def bf(x):
-    return x.to(torch.bfloat16).to(torch.float64)
-
-
-def _gemm(a, b, k, ksplit, bias=None):
-    """(expected, bound) of bf(a) @ bf(b) + bias, float64."""
-    a, b = bf(a), bf(b)
-    exp = a @ b
-    mag = a.abs() @ b.abs()
-    if bias is not None:
-        exp = exp + bias.to(torch.float64)
-        mag = mag + bias.to(torch.float64).abs()
-    return exp, (k + ksplit + 2) * U * mag
-
-
-def _close(got, exp, bound, what):
-    err = (got.to(torch.float64) - exp).abs()
-    worst = float((err - bound).max())
-    print(f"{what}: max err {float(err.max()):.3e}, "
-          f"max bound {float(bound.max()):.3e}")
-    assert worst <= 0.0, f"{what}: error exceeds the bound by {worst:.3e}"
-
-
-def _ceil(a, b):
-    return (a + b - 1) // b
-
-
-def _ks_head(B, in_total):
-    """split-K factor of a narrow (out <= 64) forward head."""
-    ntm, ks = _ceil(B, 64), 1
-    while ntm * ks < 512 and ks * 64 <= in_total:
-        ks *= 2
-    return ks
-
-
-def _ks_dw(B, in_n, out):
-    """split-K factor of one dW GEMM."""
-    nt, ks = _ceil(in_n, 64) * _ceil(out, 128), 1
-    while nt * ks < 256 and ks * 64 <= B:
-        ks *= 2
-    return ks
-
-
-class Net:
-    """One net's slab cut into per-layer [in][out] weights and biases."""
-
-    def __init__(self, slab, layers):
-        self.layers = layers
-        self.w, self.b = [], []
-        for l in layers:
-            n_in = l["in1"] + l["in2"]
-            self.w.append(slab[l["w_off"]:l["w_off"] + n_in * l["out"]]
-                          .reshape(n_in, l["out"]))
-            self.b.append(slab[l["b_off"]:l["b_off"] + l["out"]])
-
-
-def _check_fwd(buf, net, i, x, got, act, B, what):
-    l = net.layers[i]
-    n_in = l["in1"] + l["in2"]
-    ks = _ks_head(B, n_in) if l["out"] <= 64 else 1
-    exp, bound = _gemm(x, net.w[i], n_in, ks, net.b[i])
-    if act == "relu":
-        exp = exp.clamp_min(0)
-    elif act == "tanh":
-        exp, bound = exp.tanh(), torch.full_like(exp, 5e-5)
-    elif act == "softmax":
-        exp, bound = exp.softmax(1), torch.full_like(exp, 5e-5)
-    _close(buf[got], exp, bound, what)
-
-
-def _check_dx(net, i, dz, mask_h, got, what):
-    """dx1 = (dz @ W[:in1]^T) * relu'(mask_h)."""
-    l = net.layers[i]
-    exp, bound = _gemm(dz, net.w[i][:l["in1"]].t(), l["out"], 1)
-    if mask_h is not None:
-        m = (mask_h > 0).to(torch.float64)
-        exp, bound = exp * m, bound * m
-    _close(got, exp, bound, what)
-
-
-def _check_dw(net, g, i, dz, x1, x2, B, what):
-    """The layer's block of the gradient slab: dWt (per input block, as the
-    engine runs it) and db."""
-    l = net.layers[i]
-    gnet = Net(g, net.layers)
-    lo = 0
-    for x in (x1, x2):
-        if x is None:
-            continue
-        n = x.shape[1]
-        ks = _ks_dw(B, n, l["out"])
-        exp, bound = _gemm(x.t(), dz, B, ks)
-        _close(gnet.w[i][lo:lo + n], exp, bound, f"{what} dW[{lo}:{lo + n}]")
-        lo += n
-    ks = _ks_dw(B, l["in1"], l["out"])
-    exp, bound = _gemm(torch.ones(1, B), dz, B, ks)
-    _close(gnet.b[i], exp[0], bound[0], f"{what} db")
-
-
-# ---------------------------------------------------------------------------
-# 1. teacher-forced, GEMM by GEMM
+# 1. teacher-forced, GEMM by GEMM (the harness is tests/_wide_gemm.py)
 # ---------------------------------------------------------------------------
 
 @pytest.fixture(scope="module", params=sorted(CONFIGS))
 def phased(request):
-    """One bf16 engine per config, stepped phase by phase; every buffer and
-    slab read after the phase that wrote it."""
-    c = CONFIGS[request.param]
-    eng = _engine(c)
-    info = eng.info()
-    assert info["gemm_precision"] == "bf16"
-    st = {"cfg": c, "name": request.param, "info": info}
-    st["slabs0"] = {n: eng.store_slab(n) for n in SLABS}
-    eng.step_part(eng.PH_CRITIC_GRADS)
-    st["critic"] = {n: eng.read(n) for n in CRITIC_BUFS}
-    st["g_critic"] = eng.store_slab("g_critic")
-    eng.step_part(eng.PH_CRITIC_APPLY)
-    st["p_critic1"] = eng.store_slab("critic")
-    eng.step_part(eng.PH_ACTOR_GRADS)
-    st["actor"] = {n: eng.read(n) for n in ACTOR_BUFS}
-    st["g_actor"] = eng.store_slab("g_actor")
-    return st
+    return run_phased(request.param, "bf16")
 
 
 def test_critic_phase_gemm_by_gemm(phased):
-    c, buf, info = phased["cfg"], phased["critic"], phased["info"]
-    B = c["B"]
-    s0 = phased["slabs0"]
-    at = Net(s0["actor_target"], info["actor_layers"])
-    ct = Net(s0["critic_target"], info["critic_layers"])
-    cr = Net(s0["critic"], info["critic_layers"])
-    cat = lambda a, b: torch.cat([buf[a], buf[b]], 1)
-    fwd = lambda *a: _check_fwd(buf, *a)
-    # target actor
-    fwd(at, 0, buf["bs2"], "at_h1", "relu", B, "at.L1")
-    fwd(at, 1, buf["at_h1"], "at_h2", None, B, "at.L2")
-    fwd(at, 2, buf["at_h2"], "at_h3", "relu", B, "at.L3")
-    fwd(at, 3, buf["at_h3"], "a2", "tanh", B, "at.L4")
-    # target critic
-    fwd(ct, 0, buf["bs2"], "ct_h1", "relu", B, "ct.L1")
-    fwd(ct, 1, cat("ct_h1", "a2"), "ct_h2", "relu", B, "ct.L2")
-    fwd(ct, 2, buf["ct_h2"], "ct_h3", "relu", B, "ct.L3")
-    fwd(ct, 3, buf["ct_h3"], "p_t", "softmax", B, "ct.L4")
-    # critic
-    fwd(cr, 0, buf["bs"], "c_h1", "relu", B, "c.L1")
-    fwd(cr, 1, cat("c_h1", "ba"), "c_h2", "relu", B, "c.L2")
-    fwd(cr, 2, buf["c_h2"], "c_h3", "relu", B, "c.L3")
-    fwd(cr, 3, buf["c_h3"], "q", "softmax", B, "c.L4")
-    # critic backward
-    _check_dx(cr, 3, buf["dlog"], buf["c_h3"], buf["d3"], "c.L4 dX")
-    _check_dx(cr, 2, buf["d3"], buf["c_h2"], buf["d2"], "c.L3 dX")
-    _check_dx(cr, 1, buf["d2"], buf["c_h1"], buf["d1"], "c.L2 dX")
-    g = phased["g_critic"]
-    _check_dw(cr, g, 3, buf["dlog"], buf["c_h3"], None, B, "c.L4")
-    _check_dw(cr, g, 2, buf["d3"], buf["c_h2"], None, B, "c.L3")
-    _check_dw(cr, g, 1, buf["d2"], buf["c_h1"], buf["ba"], B, "c.L2")
-    _check_dw(cr, g, 0, buf["d1"], buf["bs"], None, B, "c.L1")
+    check_critic_phase(phased)
 
 
 def test_actor_phase_gemm_by_gemm(phased):
-    c, buf, info = phased["cfg"], phased["actor"], phased["info"]
-    B = c["B"]
-    ac = Net(phased["slabs0"]["actor"], info["actor_layers"])
-    cr = Net(phased["p_critic1"], info["critic_layers"])  # after its Adam
-    fwd = lambda *a: _check_fwd(buf, *a)
-    fwd(ac, 0, buf["bs"], "pa_h1", "relu", B, "a.L1")
-    fwd(ac, 1, buf["pa_h1"], "pa_h2", None, B, "a.L2")
-    fwd(ac, 2, buf["pa_h2"], "pa_h3", "relu", B, "a.L3")
-    fwd(ac, 3, buf["pa_h3"], "a_out", "tanh", B, "a.L4")
-    fwd(cr, 0, buf["bs"], "pc_h1", "relu", B, "c'.L1")
-    fwd(cr, 1, torch.cat([buf["pc_h1"], buf["a_out"]], 1), "pc_h2", "relu",
-        B, "c'.L2")
-    fwd(cr, 2, buf["pc_h2"], "pc_h3", "relu", B, "c'.L3")
-    fwd(cr, 3, buf["pc_h3"], "pq", "softmax", B, "c'.L4")
-    # dX back through the critic
-    _check_dx(cr, 3, buf["pd3"], buf["pc_h3"], buf["pd2"], "c'.L4 dX")
-    _check_dx(cr, 2, buf["pd2"], buf["pc_h2"], buf["pdh1"], "c'.L3 dX")
-    # the action slice is k_dx_narrow: plain fp32, unrounded operands
-    l = cr.layers[1]
-    dz, w = buf["pdh1"].double(), cr.w[1][l["in1"]:].double()
-    _close(buf["pda"], dz @ w.t(), (l["out"] + 2) * U * (dz.abs() @ w.abs().t()),
-           "c'.L2 dX (action slice, fp32)")
-    # actor backward
-    _check_dx(ac, 3, buf["adz"], buf["pa_h3"], buf["az3"], "a.L4 dX")
-    _check_dx(ac, 2, buf["az3"], None, buf["az2"], "a.L3 dX")
-    _check_dx(ac, 1, buf["az2"], buf["pa_h1"], buf["az1"], "a.L2 dX")
-    g = phased["g_actor"]
-    _check_dw(ac, g, 3, buf["adz"], buf["pa_h3"], None, B, "a.L4")
-    _check_dw(ac, g, 2, buf["az3"], buf["pa_h2"], None, B, "a.L3")
-    _check_dw(ac, g, 1, buf["az2"], buf["pa_h1"], None, B, "a.L2")
-    _check_dw(ac, g, 0, buf["az1"], buf["bs"], None, B, "a.L1")
+    check_actor_phase(phased)
 
 
 # ---------------------------------------------------------------------------
