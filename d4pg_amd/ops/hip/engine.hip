@@ -19,9 +19,13 @@
 //
 // This file is the single translation unit ext.hip includes.  The device
 // code lives in the parts included here, in dependency order (fragments,
-// not stand-alone sources); the host side, the Engine class, follows them:
-// device pool layout, the launch sequences of the three paths, hipGraph
-// capture and replay, replay ingestion, parameter I/O, the rollout driver.
+// not stand-alone sources), then engine_host.hip, the host support; the
+// host side, the Engine class, follows them: device pool layout, the launch
+// sequences of the three paths, hipGraph capture and replay, replay
+// ingestion, parameter I/O, the rollout driver.  Every device allocation of
+// the engine is a DevicePool, every captured graph a GraphSlot, every stream
+// and event an owning handle, and every kernel launch goes through the
+// checked launch() (all in engine_host.hip).
 
 #include <string>
 
@@ -40,6 +44,7 @@
 #include "engine_mfma.hip"
 #include "engine_mfma_bf16.hip"
 #include "engine_persistent.hip"
+#include "engine_host.hip"
 
 namespace d4pg {
 
@@ -78,13 +83,37 @@ static Net make_critic_net(int O, int A, int H, int K) {
     return make_net({{O, 0, H}, {H, A, H}, {H, 0, H}, {H, 0, K}});
 }
 
+// Host forms of the env observations, for the state-injection test hooks of
+// the rollouts and the evaluation.  Pendulum: [cos th, sin th, thdot].
+static std::vector<float> pendulum_obs(const float* th, const float* thdot,
+                                       long n) {
+    std::vector<float> obs(3 * n);
+    for (long i = 0; i < n; ++i) {
+        obs[i * 3 + 0] = cosf(th[i]);
+        obs[i * 3 + 1] = sinf(th[i]);
+        obs[i * 3 + 2] = thdot[i];
+    }
+    return obs;
+}
+
+// GoalReach: [pos, goal], D of each.
+static std::vector<float> goal_obs(const float* pos, const float* goal,
+                                   long n, long D) {
+    std::vector<float> obs(2 * n * D);
+    for (long i = 0; i < n; ++i)
+        for (long k = 0; k < D; ++k) {
+            obs[i * 2 * D + k] = pos[i * D + k];
+            obs[i * 2 * D + D + k] = goal[i * D + k];
+        }
+    return obs;
+}
+
 class Engine {
 public:
     EngineCfg cfg;
     Net anet, cnet;
-    hipStream_t stream;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
+    Stream stream;
+    GraphSlot train_graph_;             // graph_steps train steps
     int graph_steps = 0;
 
     // step geometry + every workspace pointer, as the kernels take them
@@ -126,7 +155,8 @@ public:
             ws.al[i] = anet.l[i];
             ws.cl[i] = cnet.l[i];
         }
-        HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        HIP_CHECK(hipStreamCreateWithFlags(stream.put(),
+                                           hipStreamNonBlocking));
         // co-residency gate for the persistent path: all PNWG workgroups
         // must fit on the device at once or the software grid barrier
         // cannot make progress
@@ -172,8 +202,8 @@ public:
                              double* min_tree, long tree_cap) {
         if (!sum_tree) return;
         for (long lo = tree_cap / 2; lo >= 1; lo >>= 1)
-            hipLaunchKernelGGL(k_tree_build_level, dim3(wgs), dim3(256), 0,
-                               st, sum_tree, min_tree, lo, 2 * lo);
+            launch(k_tree_build_level, wgs, 256, 0, st, sum_tree, min_tree,
+                   lo, 2 * lo);
     }
 
     // the persistent grid barrier's timeout flag (gbar[176]); raised on
@@ -189,102 +219,68 @@ public:
                 "passed but the grid did not make progress");
     }
 
+    // The one ordering rule of the engine's lifetime, spelled out here and
+    // not left to member declaration order: drain the rollout stream FIRST
+    // (an open window's episodes read and write the pools), then release
+    // graphs and pools, then events and streams.
     ~Engine() {
-        // drain the rollout stream first: an open window's episodes read
-        // and write the pools freed below
-        if (roll_stream_) hipStreamSynchronize(roll_stream_);
-        collect_pending_ = false;
-        rollout_free();
-        if (ev_snap_) hipEventDestroy(ev_snap_);
-        if (ev_done_) hipEventDestroy(ev_done_);
-        if (roll_stream_) hipStreamDestroy(roll_stream_);
-        if (graph_exec) hipGraphExecDestroy(graph_exec);
-        if (graph) hipGraphDestroy(graph);
-        hipStreamDestroy(stream);
-        hipFree(pool_);
+        if (roll_stream_) (void)hipStreamSynchronize(roll_stream_);
+        for (GraphSlot* g : {&train_graph_, &roll_graph_, &stage_graph_,
+                             &eval_graph_})
+            g->reset();
+        for (DevicePool* p : {&pool_, &roll_pool_, &stage_pool_, &eval_pool_})
+            p->reset();
+        ev_snap_.reset();
+        ev_done_.reset();
+        roll_stream_.reset();
+        stream.reset();
     }
 
-    void* pool_ = nullptr;
+    DevicePool pool_;
 
-    template <typename T>
-    T* carve(long nelem, long& off) {
-        long bytes = nelem * (long)sizeof(T);
-        bytes = (bytes + 255) & ~255L;
-        T* p = reinterpret_cast<T*>(static_cast<char*>(pool_) + off);
-        off += bytes;
-        return p;
-    }
-
-    // One carve sequence, executed twice (count pass with null base, then
-    // assign pass) so sizes and pointers can never drift apart.
-    long layout() {
-        const int B = cfg.batch, O = cfg.obs, A = cfg.act, H = cfg.hidden,
-                  K = cfg.atoms;
+    // The main pool's carve sequence (DevicePool::build runs it twice).
+    void layout(DevicePool& p) {
+        const long B = cfg.batch, O = cfg.obs, A = cfg.act, H = cfg.hidden,
+                   K = cfg.atoms;
         const long C = cfg.capacity;
         const long pa = anet.n_params, pc = cnet.n_params;
         ing_cap = 65536;
-        long off = 0;
-        ws.p_actor = carve<float>(pa, off);
-        ws.p_actor_t = carve<float>(pa, off);
-        ws.g_actor = carve<float>(pa, off);
-        ws.p_critic = carve<float>(pc, off);
-        ws.p_critic_t = carve<float>(pc, off);
-        ws.g_critic = carve<float>(pc, off);
-        ws.m_actor = carve<float>(pa, off);
-        ws.v_actor = carve<float>(pa, off);
-        ws.m_critic = carve<float>(pc, off);
-        ws.v_critic = carve<float>(pc, off);
-        ws.rs = carve<float>(C * O, off); ws.ra = carve<float>(C * A, off);
-        ws.rr = carve<float>(C, off); ws.rs2 = carve<float>(C * O, off);
-        ws.rd = carve<float>(C, off);
+        p.take(ws.p_actor, pa); p.take(ws.p_actor_t, pa);
+        p.take(ws.g_actor, pa);
+        p.take(ws.p_critic, pc); p.take(ws.p_critic_t, pc);
+        p.take(ws.g_critic, pc);
+        p.take(ws.m_actor, pa); p.take(ws.v_actor, pa);
+        p.take(ws.m_critic, pc); p.take(ws.v_critic, pc);
+        p.take(ws.rs, C * O); p.take(ws.ra, C * A); p.take(ws.rr, C);
+        p.take(ws.rs2, C * O); p.take(ws.rd, C);
         if (has_trees()) {
-            ws.sum_tree = carve<double>(2 * ws.tree_cap, off);
-            ws.min_tree = carve<double>(2 * ws.tree_cap, off);
+            p.take(ws.sum_tree, 2 * ws.tree_cap);
+            p.take(ws.min_tree, 2 * ws.tree_cap);
         } else {
             ws.sum_tree = ws.min_tree = nullptr;
         }
-        ws.cnt = carve<Counters>(1, off);
-        ws.bs = carve<float>((long)B * O, off);
-        ws.bs_b = carve<float>((long)B * O, off);
-        ws.ba = carve<float>((long)B * A, off);
-        ws.br = carve<float>(B, off); ws.bs2 = carve<float>((long)B * O, off);
-        ws.bd = carve<float>(B, off); ws.bw = carve<float>(B, off);
-        ws.pri = carve<float>(B, off);
-        ws.bidx = carve<long>(B, off);
-        ws.at_h1 = carve<float>((long)B * H, off);
-        ws.at_h2 = carve<float>((long)B * H, off);
-        ws.at_h3 = carve<float>((long)B * H, off);
-        ws.a2 = carve<float>((long)B * A, off);
-        ws.ct_h1 = carve<float>((long)B * H, off);
-        ws.ct_h2 = carve<float>((long)B * H, off);
-        ws.ct_h3 = carve<float>((long)B * H, off);
-        ws.p_t = carve<float>((long)B * K, off);
-        ws.m_proj = carve<float>((long)B * K, off);
-        ws.c_h1 = carve<float>((long)B * H, off);
-        ws.c_h2 = carve<float>((long)B * H, off);
-        ws.c_h3 = carve<float>((long)B * H, off);
-        ws.q = carve<float>((long)B * K, off);
-        ws.dlog = carve<float>((long)B * K, off);
-        ws.d3 = carve<float>((long)B * H, off);
-        ws.d2 = carve<float>((long)B * H, off);
-        ws.d1 = carve<float>((long)B * H, off);
-        ws.da = carve<float>((long)B * A, off);
-        ws.pa_h1 = carve<float>((long)B * H, off);
-        ws.pa_h2 = carve<float>((long)B * H, off);
-        ws.pa_h3 = carve<float>((long)B * H, off);
-        ws.a_out = carve<float>((long)B * A, off);
-        ws.pc_h1 = carve<float>((long)B * H, off);
-        ws.pc_h2 = carve<float>((long)B * H, off);
-        ws.pc_h3 = carve<float>((long)B * H, off);
-        ws.pq = carve<float>((long)B * K, off);
-        ws.pd3 = carve<float>((long)B * K, off);
-        ws.pd2 = carve<float>((long)B * H, off);
-        ws.pdh1 = carve<float>((long)B * H, off);
-        ws.pda = carve<float>((long)B * A, off);
-        ws.adz = carve<float>((long)B * A, off);
-        ws.az1 = carve<float>((long)B * H, off);
-        ws.az2 = carve<float>((long)B * H, off);
-        ws.az3 = carve<float>((long)B * H, off);
+        p.take(ws.cnt, 1);
+        p.take(ws.bs, B * O); p.take(ws.bs_b, B * O); p.take(ws.ba, B * A);
+        p.take(ws.br, B); p.take(ws.bs2, B * O);
+        p.take(ws.bd, B); p.take(ws.bw, B); p.take(ws.pri, B);
+        p.take(ws.bidx, B);
+        p.take(ws.at_h1, B * H); p.take(ws.at_h2, B * H);
+        p.take(ws.at_h3, B * H); p.take(ws.a2, B * A);
+        p.take(ws.ct_h1, B * H); p.take(ws.ct_h2, B * H);
+        p.take(ws.ct_h3, B * H);
+        p.take(ws.p_t, B * K); p.take(ws.m_proj, B * K);
+        p.take(ws.c_h1, B * H); p.take(ws.c_h2, B * H); p.take(ws.c_h3, B * H);
+        p.take(ws.q, B * K); p.take(ws.dlog, B * K);
+        p.take(ws.d3, B * H); p.take(ws.d2, B * H); p.take(ws.d1, B * H);
+        p.take(ws.da, B * A);
+        p.take(ws.pa_h1, B * H); p.take(ws.pa_h2, B * H);
+        p.take(ws.pa_h3, B * H); p.take(ws.a_out, B * A);
+        p.take(ws.pc_h1, B * H); p.take(ws.pc_h2, B * H);
+        p.take(ws.pc_h3, B * H);
+        p.take(ws.pq, B * K); p.take(ws.pd3, B * K);
+        p.take(ws.pd2, B * H); p.take(ws.pdh1, B * H);
+        p.take(ws.pda, B * A); p.take(ws.adz, B * A);
+        p.take(ws.az1, B * H); p.take(ws.az2, B * H); p.take(ws.az3, B * H);
         // split-K disjoint partials: the wide step's dW (max over layers of
         // ksplit * (weights + bias)) and the MFMA heads' forward partials,
         // which actor_forward already needs at B = 512 where the step itself
@@ -292,7 +288,7 @@ public:
         // when B is no power-of-two multiple of MT_K; k_mfma_dw zero-fills
         // them
         long dwp = 0;
-        if (fwd_uses_mfma(B)) {
+        if (fwd_uses_mfma(cfg.batch)) {
             auto dw_need = [&](int in_n, int out) {
                 long v = (long)dw_ksplit(in_n, out) * ((long)in_n * out + out);
                 if (v > dwp) dwp = v;
@@ -302,35 +298,28 @@ public:
                 dw_need(l.in1, l.out);
                 if (l.in2 > 0) dw_need(l.in2, l.out);
                 if (l.out <= 64) {      // split-K head fwd partials
-                    long v2 = (long)head_ksplit(B, l.in1 + l.in2) * (long)B *
-                              l.out;
+                    long v2 = (long)head_ksplit(cfg.batch, l.in1 + l.in2) *
+                              B * l.out;
                     if (v2 > dwp) dwp = v2;
                 }
             };
             for (int i = 0; i < 4; ++i) { need(anet.l[i]); need(cnet.l[i]); }
         }
-        dw_parts = carve<float>(dwp, off);
-        ws.gbar = carve<unsigned long long>(1536, off);
-        ws.tstamp = carve<unsigned long long>(64, off);
-        ing_s = carve<float>((long)ing_cap * O, off);
-        ing_a = carve<float>((long)ing_cap * A, off);
-        ing_r = carve<float>(ing_cap, off);
-        ing_s2 = carve<float>((long)ing_cap * O, off);
-        ing_d = carve<float>(ing_cap, off);
+        p.take(dw_parts, dwp);              // zero-length below 512 rows
+        p.take(ws.gbar, 1536);
+        p.take(ws.tstamp, 64);
+        p.take(ing_s, ing_cap * O); p.take(ing_a, ing_cap * A);
+        p.take(ing_r, ing_cap);
+        p.take(ing_s2, ing_cap * O); p.take(ing_d, ing_cap);
         // gradient clipping: statistics block and per-chunk partials (last,
         // so every other buffer keeps its offset)
-        ws.gstat = carve<GradStats>(1, off);
-        ws.gn_part_a = carve<double>(gn_chunks(pa), off);
-        ws.gn_part_c = carve<double>(gn_chunks(pc), off);
-        return off;
+        p.take(ws.gstat, 1);
+        p.take(ws.gn_part_a, gn_chunks(pa));
+        p.take(ws.gn_part_c, gn_chunks(pc));
     }
 
     void alloc() {
-        pool_ = nullptr;
-        long total = layout();               // count pass (null base)
-        HIP_CHECK(hipMalloc(&pool_, total));
-        HIP_CHECK(hipMemset(pool_, 0, total));
-        layout();                            // assign pass
+        pool_.build([&](DevicePool& p) { layout(p); });
         Counters h{};
         h.max_priority = 1.0f;
         // schedule counters pre-advanced: k_per_update increments at step
@@ -344,8 +333,8 @@ public:
         // min-tree neutral element is +inf (memset zero would make every
         // unoccupied leaf the minimum and zero out all IS weights)
         if (has_trees())
-            hipLaunchKernelGGL(k_fill_f64, dim3(1024), dim3(256), 0, nullptr,
-                               ws.min_tree, 2 * ws.tree_cap, HUGE_VAL);
+            launch(k_fill_f64, 1024, 256, 0, nullptr, ws.min_tree,
+                   2 * ws.tree_cap, HUGE_VAL);
         HIP_CHECK(hipDeviceSynchronize());
     }
 
@@ -392,8 +381,7 @@ public:
     // (the launchers the rollout uses take their stream; the train step's
     // run on the engine's)
     void launch_fwd_valu(const FwdJob& j, hipStream_t st) {
-        hipLaunchKernelGGL(k_fwd, dim3(j.nwg_b * j.nwg_o), dim3(256), 0,
-                           st, j);
+        launch(k_fwd, j.nwg_b * j.nwg_o, 256, 0, st, j);
     }
     void launch_fwd_valu(const FwdJob& j) { launch_fwd_valu(j, stream); }
 
@@ -401,10 +389,9 @@ public:
     // and arguments — only the wide train step in gemm_bf16 mode passes it.
     void launch_fwd_mfma(const FwdJob& j, bool bf16, hipStream_t st) {
         int ntm = ceil_div(j.B, MT_M), ntn = ceil_div(j.out, MT_N);
-        hipLaunchKernelGGL(bf16 ? k_mfma_fwd_bf16 : k_mfma_fwd,
-                           dim3(ntm * ntn), dim3(256), 0, st,
-                           j.x1, j.x2, j.wt, j.bias, j.y, j.B, j.in1, j.in2,
-                           j.out, j.act, 1, (float*)nullptr);
+        launch(bf16 ? k_mfma_fwd_bf16 : k_mfma_fwd, ntm * ntn, 256, 0, st,
+               j.x1, j.x2, j.wt, j.bias, j.y, j.B, j.in1, j.in2, j.out,
+               j.act, 1, nullptr);
     }
     void launch_fwd_mfma(const FwdJob& j, bool bf16 = false) {
         launch_fwd_mfma(j, bf16, stream);
@@ -416,14 +403,12 @@ public:
     void launch_fwd_mfma_head(const FwdJob& j, bool bf16 = false) {
         int ntm = ceil_div(j.B, MT_M);
         int ks = head_ksplit(j.B, j.in1 + j.in2);
-        hipLaunchKernelGGL(bf16 ? k_mfma_fwd_bf16 : k_mfma_fwd,
-                           dim3(ntm * ks), dim3(256), 0, stream,
-                           j.x1, j.x2, j.wt, j.bias, j.y, j.B, j.in1, j.in2,
-                           j.out, j.act, ks, dw_parts);
+        launch(bf16 ? k_mfma_fwd_bf16 : k_mfma_fwd, ntm * ks, 256, 0, stream,
+               j.x1, j.x2, j.wt, j.bias, j.y, j.B, j.in1, j.in2, j.out,
+               j.act, ks, dw_parts);
         if (ks > 1)
-            hipLaunchKernelGGL(k_head_finish, dim3(256), dim3(256), 0,
-                               stream, dw_parts, j.bias, j.y, j.B, j.out, ks,
-                               j.act);
+            launch(k_head_finish, 256, 256, 0, stream, dw_parts, j.bias, j.y,
+                   j.B, j.out, ks, j.act);
     }
 
     // Layers of one phase over the engine's batch (independent of each
@@ -465,44 +450,38 @@ public:
                 int ntm = ceil_div(in_n, MT_M);
                 int ntn = ceil_div(l.out, MT_N);
                 int ksplit = dw_ksplit(in_n, l.out);
-                hipLaunchKernelGGL(k_dw, dim3(ntm * ntn * ksplit),
-                                   dim3(256), 0, stream, dz, xop,
-                                   (const float*)nullptr, dwt, db,
-                                   cfg.batch, in_n, 0, l.out, ksplit,
-                                   dw_parts);
+                launch(k_dw, ntm * ntn * ksplit, 256, 0, stream, dz, xop,
+                       nullptr, dwt, db, cfg.batch, in_n, 0, l.out, ksplit,
+                       dw_parts);
                 if (ksplit > 1)
-                    hipLaunchKernelGGL(k_dw_reduce, dim3(1024), dim3(256),
-                                       0, stream, dw_parts, dwt, db,
-                                       (long)in_n * l.out, l.out, ksplit);
+                    launch(k_dw_reduce, 1024, 256, 0, stream, dw_parts, dwt,
+                           db, (long)in_n * l.out, l.out, ksplit);
             };
             dw_gemm(x1, l.in1, gslab + l.w_off, gslab + l.b_off);
             if (l.in2 > 0)
                 dw_gemm(x2, l.in2, gslab + l.w_off + (long)l.in1 * l.out,
-                        (float*)nullptr);
+                        nullptr);
         }
         if (dx1) {
             int ntm = ceil_div(cfg.batch, MT_M);
             int ntn = ceil_div(l.in1, MT_N);
-            hipLaunchKernelGGL(k_dx, dim3(ntm * ntn), dim3(256), 0,
-                               stream, dz, slab + l.w_off, h1, dx1,
-                               cfg.batch, 0, l.in1, l.out, prev_act);
+            launch(k_dx, ntm * ntn, 256, 0, stream, dz, slab + l.w_off, h1,
+                   dx1, cfg.batch, 0, l.in1, l.out, prev_act);
         }
         if (dx2) {
             if (l.in2 <= 8) {
                 // action slice: wave-per-row VALU beats a 1-N-tile MFMA
                 // grid by ~7x here (see k_dx_narrow comment); fp32 in
                 // either precision mode
-                hipLaunchKernelGGL(k_dx_narrow, dim3(256), dim3(256), 0,
-                                   stream, dz, slab + l.w_off,
-                                   (const float*)nullptr, dx2, cfg.batch,
-                                   l.in1, in_total, l.out, ACT_NONE);
+                launch(k_dx_narrow, 256, 256, 0, stream, dz, slab + l.w_off,
+                       nullptr, dx2, cfg.batch, l.in1, in_total, l.out,
+                       ACT_NONE);
             } else {
                 int ntm = ceil_div(cfg.batch, MT_M);
                 int ntn = ceil_div(l.in2, MT_N);
-                hipLaunchKernelGGL(k_dx, dim3(ntm * ntn), dim3(256),
-                                   0, stream, dz, slab + l.w_off,
-                                   (const float*)nullptr, dx2, cfg.batch,
-                                   l.in1, in_total, l.out, ACT_NONE);
+                launch(k_dx, ntm * ntn, 256, 0, stream, dz, slab + l.w_off,
+                       nullptr, dx2, cfg.batch, l.in1, in_total, l.out,
+                       ACT_NONE);
             }
         }
     }
@@ -535,12 +514,8 @@ public:
     }
 
     void enqueue_persistent(int nsteps) {
-        if (clip())
-            hipLaunchKernelGGL(k_step_persistent<true>, dim3(PNWG),
-                               dim3(256), 0, stream, ws, nsteps);
-        else
-            hipLaunchKernelGGL(k_step_persistent<false>, dim3(PNWG),
-                               dim3(256), 0, stream, ws, nsteps);
+        launch(clip() ? k_step_persistent<true> : k_step_persistent<false>,
+               PNWG, 256, 0, stream, ws, nsteps);
     }
 
     // All four layers' weight gradients of one net in a single k_bwd4
@@ -560,13 +535,11 @@ public:
             j[i].nwg_dw_o = ceil_div(l.out, BWT);
             wg += j[i].nwg_dw_i * j[i].nwg_dw_o;
         }
-        hipLaunchKernelGGL(k_bwd4, dim3(wg), dim3(256), 0, stream,
-                           j[0], j[1], j[2], j[3]);
+        launch(k_bwd4, wg, 256, 0, stream, j[0], j[1], j[2], j[3]);
     }
 
     void launch_per_sample() {
-        hipLaunchKernelGGL(k_per_sample, dim3(ceil_div(cfg.batch, 4)),
-                           dim3(256), 0, stream, ws);
+        launch(k_per_sample, ceil_div(cfg.batch, 4), 256, 0, stream, ws);
     }
 
     // Adam + target soft-update of one net, fused.  With clipping on, the
@@ -574,40 +547,27 @@ public:
     // a data-parallel all-reduce, and inside captured graphs) and the
     // clip-on Adam kernel reads the scale from the statistics block.
     void launch_adam_lerp(bool is_actor) {
-        if (clip()) {
-            const float* g = is_actor ? ws.g_actor : ws.g_critic;
-            double* part = is_actor ? ws.gn_part_a : ws.gn_part_c;
-            const long n = is_actor ? anet.n_params : cnet.n_params;
-            hipLaunchKernelGGL(k_grad_norm, dim3(gn_chunks(n)), dim3(256), 0,
-                               stream, g, n, part);
-            hipLaunchKernelGGL(k_grad_finish, dim3(1), dim3(64), 0, stream,
-                               part, n, cfg.max_grad_norm, ws.gstat,
-                               is_actor ? 1 : 0);
-            if (is_actor)
-                hipLaunchKernelGGL(k_adam_lerp_clip, dim3(256), dim3(256), 0,
-                                   stream, ws.p_actor, ws.g_actor, ws.m_actor,
-                                   ws.v_actor, ws.p_actor_t, anet.n_params,
-                                   cfg.lr_actor, 0.9f, 0.999f, 1e-8f, cfg.tau,
-                                   ws.cnt, 1, ws.gstat);
-            else
-                hipLaunchKernelGGL(k_adam_lerp_clip, dim3(256), dim3(256), 0,
-                                   stream, ws.p_critic, ws.g_critic,
-                                   ws.m_critic, ws.v_critic, ws.p_critic_t,
-                                   cnet.n_params, cfg.lr_critic, 0.9f, 0.999f,
-                                   1e-8f, cfg.tau, ws.cnt, 0, ws.gstat);
+        float *p = ws.p_critic, *g = ws.g_critic, *m = ws.m_critic,
+              *v = ws.v_critic, *tgt = ws.p_critic_t;
+        double* part = ws.gn_part_c;
+        long n = cnet.n_params;
+        float lr = cfg.lr_critic;
+        if (is_actor) {
+            p = ws.p_actor; g = ws.g_actor; m = ws.m_actor; v = ws.v_actor;
+            tgt = ws.p_actor_t; part = ws.gn_part_a;
+            n = anet.n_params; lr = cfg.lr_actor;
+        }
+        const int ia = is_actor ? 1 : 0;
+        if (!clip()) {
+            launch(k_adam_lerp, 256, 256, 0, stream, p, g, m, v, tgt, n, lr,
+                   0.9f, 0.999f, 1e-8f, cfg.tau, ws.cnt, ia);
             return;
         }
-        if (is_actor)
-            hipLaunchKernelGGL(k_adam_lerp, dim3(256), dim3(256), 0, stream,
-                               ws.p_actor, ws.g_actor, ws.m_actor, ws.v_actor,
-                               ws.p_actor_t, anet.n_params, cfg.lr_actor,
-                               0.9f, 0.999f, 1e-8f, cfg.tau, ws.cnt, 1);
-        else
-            hipLaunchKernelGGL(k_adam_lerp, dim3(256), dim3(256), 0, stream,
-                               ws.p_critic, ws.g_critic, ws.m_critic,
-                               ws.v_critic, ws.p_critic_t, cnet.n_params,
-                               cfg.lr_critic, 0.9f, 0.999f, 1e-8f, cfg.tau,
-                               ws.cnt, 0);
+        launch(k_grad_norm, gn_chunks(n), 256, 0, stream, g, n, part);
+        launch(k_grad_finish, 1, 64, 0, stream, part, n, cfg.max_grad_norm,
+               ws.gstat, ia);
+        launch(k_adam_lerp_clip, 256, 256, 0, stream, p, g, m, v, tgt, n, lr,
+               0.9f, 0.999f, 1e-8f, cfg.tau, ws.cnt, ia, ws.gstat);
     }
 
     void enqueue_step_rowblock(int mask) {
@@ -616,8 +576,7 @@ public:
         long smem = rb_lds_bytes(H);
         if (mask & PH_CRITIC_GRADS) {
             launch_per_sample();
-            hipLaunchKernelGGL(k_critic_rowblock, dim3(row_wgs), dim3(256),
-                               smem, stream, ws);
+            launch(k_critic_rowblock, row_wgs, 256, smem, stream, ws);
             launch_dw4({{ws.d1, ws.bs, nullptr},
                         {ws.d2, ws.c_h1, ws.ba},
                         {ws.d3, ws.c_h2, nullptr},
@@ -626,8 +585,7 @@ public:
         }
         if (mask & PH_CRITIC_APPLY) launch_adam_lerp(false);
         if (mask & PH_ACTOR_GRADS) {
-            hipLaunchKernelGGL(k_policy_rowblock, dim3(row_wgs), dim3(256),
-                               smem, stream, ws);
+            launch(k_policy_rowblock, row_wgs, 256, smem, stream, ws);
             launch_dw4({{ws.az1, ws.bs, nullptr},
                         {ws.az2, ws.pa_h1, nullptr},
                         {ws.az3, ws.pa_h2, nullptr},
@@ -637,13 +595,11 @@ public:
         if (mask & PH_ACTOR_APPLY) {
             launch_adam_lerp(true);
             if (has_trees())
-                hipLaunchKernelGGL(k_per_update, dim3(1), dim3(256), 0,
-                                   stream, ws.sum_tree, ws.min_tree,
-                                   ws.tree_cap, ws.bidx, ws.pri, B,
-                                   cfg.per_alpha, ws.cnt);
+                launch(k_per_update, 1, 256, 0, stream, ws.sum_tree,
+                       ws.min_tree, ws.tree_cap, ws.bidx, ws.pri, B,
+                       cfg.per_alpha, ws.cnt);
             else            // the counters still tick once per step
-                hipLaunchKernelGGL(k_tick_end, dim3(1), dim3(64), 0, stream,
-                                   ws.cnt);
+                launch(k_tick_end, 1, 64, 0, stream, ws.cnt);
         }
     }
 
@@ -688,13 +644,11 @@ public:
         launch_fwd({fwd_job(ws.ct_h3, nullptr, ws.p_critic_t, cnet.l[3], ws.p_t,
                             ACT_SOFTMAX)}, bf);
         // P9+P10 fused: projection + CE grad + priorities
-        hipLaunchKernelGGL(k_project_ce, dim3(min(row_wgs, 256)),
-                           dim3(256),
-                           waves_per_wg * 64 * sizeof(float), stream,
-                           ws.p_t, ws.br, ws.bd, ws.q, ws.bw, ws.m_proj,
-                           ws.dlog, ws.pri, ws.cnt,
-                           B, K, cfg.v_min, cfg.v_max, cfg.gamma_n,
-                           cfg.per_eps, cfg.is_weighting, cfg.true_td);
+        launch(k_project_ce, min(row_wgs, 256), 256,
+               waves_per_wg * 64 * sizeof(float), stream,
+               ws.p_t, ws.br, ws.bd, ws.q, ws.bw, ws.m_proj, ws.dlog, ws.pri,
+               ws.cnt, B, K, cfg.v_min, cfg.v_max, cfg.gamma_n, cfg.per_eps,
+               cfg.is_weighting, cfg.true_td);
         // P11-14: critic backward L4..L1
         launch_bwd(ws.dlog, ws.c_h3, nullptr, ws.p_critic, ws.g_critic,
                    cnet.l[3], ws.d3, nullptr, ws.c_h3, ACT_RELU, true, bf);
@@ -728,9 +682,8 @@ public:
         launch_fwd({fwd_job(ws.pc_h3, nullptr, ws.p_critic, cnet.l[3], ws.pq,
                             ACT_SOFTMAX)}, bf);
         // P23: policy head gradient
-        hipLaunchKernelGGL(k_policy_grad, dim3(min(row_wgs, 256)),
-                           dim3(256), 0, stream,
-                           ws.pq, ws.pd3, ws.cnt, B, K, cfg.v_min, cfg.v_max);
+        launch(k_policy_grad, min(row_wgs, 256), 256, 0, stream, ws.pq,
+               ws.pd3, ws.cnt, B, K, cfg.v_min, cfg.v_max);
         // P24-26: dX back through critic' (no dW), ending at da
         launch_bwd(ws.pd3, ws.pc_h3, nullptr, ws.p_critic, nullptr, cnet.l[3],
                    ws.pd2, nullptr, ws.pc_h3, ACT_RELU, false, bf);
@@ -739,9 +692,8 @@ public:
         launch_bwd(ws.pdh1, ws.pc_h1, ws.a_out, ws.p_critic, nullptr, cnet.l[1],
                    nullptr, ws.pda, ws.pc_h1, ACT_RELU, false, bf);
         // P27: tanh backward at actor output
-        hipLaunchKernelGGL(k_tanh_bwd, dim3(ceil_div((long)B * cfg.act, 256)),
-                           dim3(256), 0, stream, ws.pda, ws.a_out, ws.adz,
-                           (long)B * cfg.act);
+        launch(k_tanh_bwd, ceil_div((long)B * cfg.act, 256), 256, 0, stream,
+               ws.pda, ws.a_out, ws.adz, (long)B * cfg.act);
         // P28-31: actor backward L4..L1 (with dW).  az3/az2/az1 are the
         // deltas at the actor's layers 3/2/1, the names they carry on the
         // row-block path: every GEMM's dz outlives the phase (read_buffer)
@@ -761,22 +713,20 @@ public:
         // P34: PER priority write-back by the per-level grid-wide repair
         // (the one-wg level-synced k_per_update serializes at this size)
         if (has_trees()) {
-        hipLaunchKernelGGL(k_per_leaves, dim3(ceil_div(B, 256)),
-                           dim3(256), 0, stream, ws.sum_tree, ws.min_tree,
-                           ws.tree_cap, ws.bidx, ws.pri, B, cfg.per_alpha,
-                           ws.cnt);
+        launch(k_per_leaves, ceil_div(B, 256), 256, 0, stream, ws.sum_tree,
+               ws.min_tree, ws.tree_cap, ws.bidx, ws.pri, B, cfg.per_alpha,
+               ws.cnt);
         long levels = 0;
         for (long c = ws.tree_cap; c > 1; c >>= 1) ++levels;
         // 4 heights per dispatch (k_per_level4): 20 launches -> 5
         for (long h0 = 0; h0 < levels; h0 += 4) {
             int nlv = (int)((levels - h0) < 4 ? (levels - h0) : 4);
-            hipLaunchKernelGGL(k_per_level4,
-                               dim3(ceil_div((long)B * nlv, 256)),
-                               dim3(256), 0, stream, ws.sum_tree, ws.min_tree,
-                               ws.tree_cap, ws.bidx, B, h0, nlv);
+            launch(k_per_level4, ceil_div((long)B * nlv, 256), 256, 0, stream,
+                   ws.sum_tree, ws.min_tree, ws.tree_cap, ws.bidx, B, h0,
+                   nlv);
         }
         }
-        hipLaunchKernelGGL(k_tick_end, dim3(1), dim3(64), 0, stream, ws.cnt);
+        launch(k_tick_end, 1, 64, 0, stream, ws.cnt);
     }
 
     void enqueue_step(int mask = PH_ALL) {
@@ -811,41 +761,36 @@ public:
     }
 
     void invalidate_graph() {
-        if (graph_exec) { hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
-        if (graph) { hipGraphDestroy(graph); graph = nullptr; }
+        train_graph_.reset();
         graph_steps = 0;
     }
 
     void capture(int steps_per_graph) {
         invalidate_graph();
-        HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        for (int i = 0; i < steps_per_graph; ++i) enqueue_step();
-        HIP_CHECK(hipStreamEndCapture(stream, &graph));
-        HIP_CHECK(hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
+        train_graph_.ensure(stream, [&] {
+            for (int i = 0; i < steps_per_graph; ++i) enqueue_step();
+        });
         graph_steps = steps_per_graph;
     }
 
     void replay(int iters) {
-        if (!graph_exec) throw std::runtime_error("no graph captured");
-        for (int i = 0; i < iters; ++i)
-            HIP_CHECK(hipGraphLaunch(graph_exec, stream));
+        replay_async(iters);
         HIP_CHECK(hipStreamSynchronize(stream));
     }
 
     // non-blocking variants for overlap with host work
     void replay_async(int iters) {
-        for (int i = 0; i < iters; ++i)
-            HIP_CHECK(hipGraphLaunch(graph_exec, stream));
+        if (!train_graph_) throw std::runtime_error("no graph captured");
+        for (int i = 0; i < iters; ++i) train_graph_.launch(stream);
     }
     void sync() { HIP_CHECK(hipStreamSynchronize(stream)); }
 
     // ------------- replay ops -------------
     void synth_fill(long n, uint64_t seed) {
         if (n > cfg.capacity) n = cfg.capacity;
-        hipLaunchKernelGGL(k_synth_fill, dim3(1024), dim3(256), 0, stream,
-                           ws.rs, ws.ra, ws.rr, ws.rs2, ws.rd, ws.sum_tree,
-                           ws.min_tree, ws.tree_cap, cfg.capacity, n, cfg.obs,
-                           cfg.act, seed, cfg.per_alpha);
+        launch(k_synth_fill, 1024, 256, 0, stream, ws.rs, ws.ra, ws.rr,
+               ws.rs2, ws.rd, ws.sum_tree, ws.min_tree, ws.tree_cap,
+               cfg.capacity, n, cfg.obs, cfg.act, seed, cfg.per_alpha);
         launch_tree_rebuild(256);
         Counters h{};
         HIP_CHECK(hipMemcpyAsync(&h, ws.cnt, sizeof(h), hipMemcpyDeviceToHost,
@@ -880,12 +825,10 @@ public:
         HIP_CHECK(hipMemcpyAsync(ing_d, hd, (long)T * 4,
                                  hipMemcpyHostToDevice, stream));
         if (T <= 4096) {
-            hipLaunchKernelGGL(k_replay_add, dim3(1), dim3(1024), 0, stream,
-                               ws.rs, ws.ra, ws.rr, ws.rs2, ws.rd,
-                               ws.sum_tree, ws.min_tree, ws.tree_cap,
-                               cfg.capacity, ing_s, ing_a, ing_r,
-                               ing_s2, ing_d, T, O, A, cfg.per_alpha, skip,
-                               ws.cnt);
+            launch(k_replay_add, 1, 1024, 0, stream, ws.rs, ws.ra, ws.rr,
+                   ws.rs2, ws.rd, ws.sum_tree, ws.min_tree, ws.tree_cap,
+                   cfg.capacity, ing_s, ing_a, ing_r, ing_s2, ing_d, T, O, A,
+                   cfg.per_alpha, skip, ws.cnt);
         } else {
             // bulk path: grid-wide copy + leaf init, then a full
             // bandwidth-bound tree rebuild (far cheaper than one wg
@@ -895,12 +838,10 @@ public:
                                      hipMemcpyDeviceToHost, stream));
             HIP_CHECK(hipStreamSynchronize(stream));
             double pa = pow((double)h.max_priority, (double)cfg.per_alpha);
-            hipLaunchKernelGGL(k_replay_copy, dim3(1024), dim3(256), 0,
-                               stream, ws.rs, ws.ra, ws.rr, ws.rs2, ws.rd,
-                               ws.sum_tree, ws.min_tree, ws.tree_cap,
-                               cfg.capacity, (h.pos + skip) % cfg.capacity,
-                               ing_s, ing_a, ing_r, ing_s2, ing_d, T, O, A,
-                               pa);
+            launch(k_replay_copy, 1024, 256, 0, stream, ws.rs, ws.ra, ws.rr,
+                   ws.rs2, ws.rd, ws.sum_tree, ws.min_tree, ws.tree_cap,
+                   cfg.capacity, (h.pos + skip) % cfg.capacity, ing_s, ing_a,
+                   ing_r, ing_s2, ing_d, T, O, A, pa);
             launch_tree_rebuild(1024);
             h.pos = (h.pos + skip + T) % cfg.capacity;
             h.size = h.size + T > cfg.capacity ? cfg.capacity : h.size + T;
@@ -958,10 +899,9 @@ public:
     // is a plain forward job with a concat input.
     float* syn_dyn_ = nullptr;
     LayerDesc syn_dyn_desc_{};
-    void* roll_pool_ = nullptr;
+    DevicePool roll_pool_;
     float *r_h1 = nullptr, *r_h2 = nullptr, *r_h3 = nullptr;
-    hipGraph_t roll_graph = nullptr;
-    hipGraphExec_t roll_graph_exec = nullptr;
+    GraphSlot roll_graph_;              // one episode, reset included
     // which producer owns roll_pool_ and the episode graph
     enum { ROLL_NONE = 0, ROLL_PENDULUM = 1, ROLL_GOAL = 2, ROLL_SYNTH = 3 };
     int roll_kind_ = ROLL_NONE;
@@ -992,10 +932,8 @@ public:
         refuse_in_window("rollout_free / *_rollout_alloc");
         collect_free();                 // the staging store of this producer
         eval_free();                    // the evaluation models this producer
-        if (roll_graph_exec) { hipGraphExecDestroy(roll_graph_exec);
-                               roll_graph_exec = nullptr; }
-        if (roll_graph) { hipGraphDestroy(roll_graph); roll_graph = nullptr; }
-        if (roll_pool_) { hipFree(roll_pool_); roll_pool_ = nullptr; }
+        roll_graph_.reset();
+        roll_pool_.reset();
         roll_kind_ = ROLL_NONE;
     }
 
@@ -1020,34 +958,17 @@ public:
     }
 
     // Frees the previous producer's pool and builds this one's.
-    // carve(sub) names each of the producer's own buffers once, as
-    // sub(pointer, nelem) in 4-byte words; the core's device words and the
-    // policy chain's hidden buffers are carved here.  carve runs twice: to
-    // size the pool, then to point the buffers into the cleared allocation.
+    // carve(pool) takes each of the producer's own buffers; the core's
+    // device words and the policy chain's hidden buffers are taken here.
     template <class Carve>
     void roll_pool_build(RollCore& c, Carve carve) {
         rollout_free();
-        char* base = nullptr;
-        long off = 0;
-        auto sub = [&](auto*& p, long nelem) {
-            if (base) p = reinterpret_cast<decltype(+p)>(base + off);
-            off += (nelem * 4 + 255) & ~255L;
-        };
-        auto carve_all = [&] {
-            off = 0;
-            carve(sub);
-            sub(c.ep_state, 16);                // 8 words of 8 bytes
+        roll_pool_.build([&](DevicePool& p) {
+            carve(p);
+            p.take(c.ep_state, 8);
             const long MH = (long)c.M * cfg.hidden;
-            sub(r_h1, MH); sub(r_h2, MH); sub(r_h3, MH);
-        };
-        carve_all();
-        HIP_CHECK(hipMalloc(&roll_pool_, off));
-        HIP_CHECK(hipMemset(roll_pool_, 0, off));
-        base = (char*)roll_pool_;
-        carve_all();
-        // the clear went to the null stream; the episode kernels run on the
-        // engine's non-blocking stream
-        HIP_CHECK(hipDeviceSynchronize());
+            p.take(r_h1, MH); p.take(r_h2, MH); p.take(r_h3, MH);
+        });
     }
 
     // the policy forward obs [M][obs] -> act [M][act] between two ticks
@@ -1083,7 +1004,7 @@ public:
         hipStream_t st = staged ? roll_stream_ : stream;
         const float* slab = staged ? p_actor_roll : ws.p_actor;
         RollCore& c = roll_core(staged);
-        hipLaunchKernelGGL(k_roll_begin, dim3(1), dim3(64), 0, st, c);
+        launch(k_roll_begin, 1, 64, 0, st, c);
         if (roll_kind_ == ROLL_GOAL)
             goal_enqueue_ticks(staged ? goal_st_ : goal_, reset, st, slab);
         else if (roll_kind_ == ROLL_SYNTH)
@@ -1100,20 +1021,11 @@ public:
     // `episodes` whole episodes and the synchronise after them; with
     // use_graph and reset, one captured graph launched once per episode
     void run_episodes(int episodes, bool reset, bool use_graph) {
-        if (use_graph && reset) {
-            if (!roll_graph_exec) {
-                HIP_CHECK(hipStreamBeginCapture(
-                    stream, hipStreamCaptureModeThreadLocal));
-                enqueue_episode(true);
-                HIP_CHECK(hipStreamEndCapture(stream, &roll_graph));
-                HIP_CHECK(hipGraphInstantiate(&roll_graph_exec, roll_graph,
-                                              nullptr, nullptr, 0));
-            }
-            for (int e = 0; e < episodes; ++e)
-                HIP_CHECK(hipGraphLaunch(roll_graph_exec, stream));
-        } else {
-            for (int e = 0; e < episodes; ++e)
-                enqueue_episode(reset);
+        if (use_graph && reset)
+            roll_graph_.ensure(stream, [&] { enqueue_episode(true); });
+        for (int e = 0; e < episodes; ++e) {
+            if (use_graph && reset) roll_graph_.launch(stream);
+            else enqueue_episode(reset);
         }
         HIP_CHECK(hipStreamSynchronize(stream));
     }
@@ -1169,7 +1081,7 @@ public:
     RollArgs roll_st_{};
     GoalRollArgs goal_st_{};
     SynRollArgs syn_st_{};
-    void* stage_pool_ = nullptr;
+    DevicePool stage_pool_;
     float *st_rs = nullptr, *st_ra = nullptr, *st_rr = nullptr,
           *st_rs2 = nullptr, *st_rd = nullptr;
     Counters* st_cnt = nullptr;
@@ -1178,17 +1090,13 @@ public:
     int collect_max_episodes_ = 0;
     int collect_episodes_ = 0;          // of the open window
     bool collect_pending_ = false;
-    hipStream_t roll_stream_ = nullptr;
-    hipEvent_t ev_snap_ = nullptr, ev_done_ = nullptr;
-    hipGraph_t stage_graph = nullptr;
-    hipGraphExec_t stage_graph_exec = nullptr;
+    Stream roll_stream_;
+    Event ev_snap_, ev_done_;
+    GraphSlot stage_graph_;             // one staged episode
 
     void collect_free() {
-        if (stage_graph_exec) { hipGraphExecDestroy(stage_graph_exec);
-                                stage_graph_exec = nullptr; }
-        if (stage_graph) { hipGraphDestroy(stage_graph);
-                           stage_graph = nullptr; }
-        if (stage_pool_) { hipFree(stage_pool_); stage_pool_ = nullptr; }
+        stage_graph_.reset();
+        stage_pool_.reset();
         collect_max_episodes_ = 0;
         stage_rows_ = 0;
     }
@@ -1222,33 +1130,22 @@ public:
             // (numerically larger = lower); the range is [0, 0] where not
             int least = 0, greatest = 0;
             HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            // (events first: the stream's presence is what marks all three)
+            HIP_CHECK(hipEventCreateWithFlags(ev_snap_.put(),
+                                              hipEventDisableTiming));
+            HIP_CHECK(hipEventCreateWithFlags(ev_done_.put(),
+                                              hipEventDisableTiming));
             HIP_CHECK(hipStreamCreateWithPriority(
-                &roll_stream_, hipStreamNonBlocking, least));
-            HIP_CHECK(hipEventCreateWithFlags(&ev_snap_,
-                                              hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&ev_done_,
-                                              hipEventDisableTiming));
+                roll_stream_.put(), hipStreamNonBlocking, least));
         }
         const long O = cfg.obs, A = cfg.act;
-        char* base = nullptr;
-        long off = 0;
-        auto sub = [&](auto*& p, long nelem) {      // nelem in 4-byte words
-            if (base) p = reinterpret_cast<decltype(+p)>(base + off);
-            off += (nelem * 4 + 255) & ~255L;
-        };
-        auto carve_all = [&] {
-            off = 0;
-            sub(st_rs, rows * O); sub(st_ra, rows * A); sub(st_rr, rows);
-            sub(st_rs2, rows * O); sub(st_rd, rows);
-            sub(st_cnt, (long)(sizeof(Counters) + 3) / 4);
-            sub(p_actor_roll, anet.n_params);
-        };
-        carve_all();
-        HIP_CHECK(hipMalloc(&stage_pool_, off));
-        HIP_CHECK(hipMemset(stage_pool_, 0, off));
-        base = (char*)stage_pool_;
-        carve_all();
-        HIP_CHECK(hipDeviceSynchronize());
+        stage_pool_.build([&](DevicePool& p) {
+            p.take(st_rs, rows * O); p.take(st_ra, rows * A);
+            p.take(st_rr, rows);
+            p.take(st_rs2, rows * O); p.take(st_rd, rows);
+            p.take(st_cnt, 1);
+            p.take(p_actor_roll, anet.n_params);
+        });
         // the producer's args over the staging store: with null trees
         // roll_leaf_value / roll_write_leaf are no-ops, and k_roll_begin,
         // k_roll_end, k_goal_end and roll_advance work on the staging words
@@ -1287,19 +1184,12 @@ public:
         if (roll_kind_ == ROLL_GOAL)    // the window's totals, as a run's
             HIP_CHECK(hipMemsetAsync(goal_st_.ep_state + 5, 0, 3 * 8,
                                      roll_stream_));
-        if (use_graph) {
-            if (!stage_graph_exec) {
-                HIP_CHECK(hipStreamBeginCapture(
-                    roll_stream_, hipStreamCaptureModeThreadLocal));
-                enqueue_episode(true, true);
-                HIP_CHECK(hipStreamEndCapture(roll_stream_, &stage_graph));
-                HIP_CHECK(hipGraphInstantiate(&stage_graph_exec, stage_graph,
-                                              nullptr, nullptr, 0));
-            }
-            for (int e = 0; e < episodes; ++e)
-                HIP_CHECK(hipGraphLaunch(stage_graph_exec, roll_stream_));
-        } else {
-            for (int e = 0; e < episodes; ++e) enqueue_episode(true, true);
+        if (use_graph)
+            stage_graph_.ensure(roll_stream_,
+                                [&] { enqueue_episode(true, true); });
+        for (int e = 0; e < episodes; ++e) {
+            if (use_graph) stage_graph_.launch(roll_stream_);
+            else enqueue_episode(true, true);
         }
         HIP_CHECK(hipEventRecord(ev_done_, roll_stream_));
     }
@@ -1329,11 +1219,9 @@ public:
         // sized for the staging store, not the (device-side) row count
         const long work = stage_rows_ * (cfg.obs > 4 ? cfg.obs / 4 : 1);
         int wgs = ceil_div(work, 256);
-        hipLaunchKernelGGL(k_stage_commit, dim3(wgs > 1024 ? 1024 : wgs),
-                           dim3(256), 0, stream, a);
+        launch(k_stage_commit, wgs > 1024 ? 1024 : wgs, 256, 0, stream, a);
         launch_tree_rebuild(1024);
-        hipLaunchKernelGGL(k_stage_commit_end, dim3(1), dim3(64), 0, stream,
-                           a);
+        launch(k_stage_commit_end, 1, 64, 0, stream, a);
         // the window is closed once its work is enqueued, whatever the
         // synchronise reports
         collect_pending_ = false;
@@ -1360,10 +1248,11 @@ public:
                   ou_sigma, ou_mu, seed);
         a.O = 3; a.A = 1;
         const long nM = (long)nsteps * M;
-        roll_pool_build(a, [&](auto& sub) {
-            sub(a.th, M); sub(a.thdot, M); sub(a.obs, 3L * M);
-            sub(a.act, M); sub(a.ou_x, M);
-            sub(a.s_ring, 3 * nM); sub(a.a_ring, nM); sub(a.r_ring, nM);
+        roll_pool_build(a, [&](DevicePool& p) {
+            p.take(a.th, M); p.take(a.thdot, M); p.take(a.obs, 3L * M);
+            p.take(a.act, M); p.take(a.ou_x, M);
+            p.take(a.s_ring, 3 * nM); p.take(a.a_ring, nM);
+            p.take(a.r_ring, nM);
         });
         roll_ = a;
         roll_kind_ = ROLL_PENDULUM;
@@ -1372,20 +1261,16 @@ public:
     void pendulum_enqueue_ticks(RollArgs& a, bool reset, hipStream_t st,
                                 const float* slab) {
         int wgs = ceil_div(a.M, 256);
-        if (reset)
-            hipLaunchKernelGGL(k_roll_reset, dim3(wgs), dim3(256), 0,
-                               st, a);
+        if (reset) launch(k_roll_reset, wgs, 256, 0, st, a);
         int emit_k = 0;
         for (int t = 0; t < a.horizon; ++t) {
             roll_fwd_chain(a.obs, a.act, a.M, st, slab);
             int ek = (t >= a.n - 1) ? emit_k : -1;
             int done = (t == a.horizon - 1) ? 1 : 0;
-            hipLaunchKernelGGL(k_roll_tick, dim3(wgs), dim3(256), 0, st,
-                               a, t, t % a.n, ek, done);
+            launch(k_roll_tick, wgs, 256, 0, st, a, t, t % a.n, ek, done);
             if (ek >= 0) ++emit_k;
         }
-        hipLaunchKernelGGL(k_roll_end, dim3(1), dim3(64), 0, st,
-                           (RollCore&)a, (long)emit_k * a.M);
+        launch(k_roll_end, 1, 64, 0, st, a, (long)emit_k * a.M);
     }
 
     void rollout_run(int episodes, bool reset, bool use_graph) {
@@ -1401,13 +1286,8 @@ public:
             throw std::runtime_error("rollout_set_state: bad M");
         HIP_CHECK(hipMemcpy(roll_.th, th, M * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(roll_.thdot, td, M * 4, hipMemcpyHostToDevice));
-        std::vector<float> obs(3 * M);
-        for (int i = 0; i < M; ++i) {
-            obs[i * 3 + 0] = cosf(th[i]);
-            obs[i * 3 + 1] = sinf(th[i]);
-            obs[i * 3 + 2] = td[i];
-        }
-        HIP_CHECK(hipMemcpy(roll_.obs, obs.data(), 3L * M * 4,
+        HIP_CHECK(hipMemcpy(roll_.obs, pendulum_obs(th, td, M).data(),
+                            3L * M * 4,
                             hipMemcpyHostToDevice));
         // as k_roll_reset leaves it: the OU process starts at mu
         std::vector<float> ou(M, roll_.ou_mu);
@@ -1444,12 +1324,13 @@ public:
         a.D = cfg.act;
         a.speed = speed; a.tol = tol; a.her_ratio = her_ratio;
         const long MD = (long)M * a.D;
-        roll_pool_build(a, [&](auto& sub) {
-            sub(a.pos, MD); sub(a.goal, MD); sub(a.obs, 2 * MD);
-            sub(a.act, MD); sub(a.ou_x, MD);
-            sub(a.alive, M); sub(a.len, M); sub(a.succ, M);
-            sub(a.ep_pos, (horizon + 1) * MD); sub(a.ep_act, horizon * MD);
-            sub(a.count, M); sub(a.offset, 2L * M);
+        roll_pool_build(a, [&](DevicePool& p) {
+            p.take(a.pos, MD); p.take(a.goal, MD); p.take(a.obs, 2 * MD);
+            p.take(a.act, MD); p.take(a.ou_x, MD);
+            p.take(a.alive, M); p.take(a.len, M); p.take(a.succ, M);
+            p.take(a.ep_pos, (horizon + 1) * MD);
+            p.take(a.ep_act, horizon * MD);
+            p.take(a.count, M); p.take(a.offset, M);
         });
         goal_ = a;
         roll_kind_ = ROLL_GOAL;
@@ -1458,22 +1339,17 @@ public:
     void goal_enqueue_ticks(GoalRollArgs& a, bool reset, hipStream_t st,
                             const float* slab) {
         int wgs = ceil_div(a.M, 256);
-        if (reset)
-            hipLaunchKernelGGL(k_goal_reset, dim3(wgs), dim3(256), 0,
-                               st, a);
+        if (reset) launch(k_goal_reset, wgs, 256, 0, st, a);
         for (int t = 0; t < a.horizon; ++t) {
             roll_fwd_chain(a.obs, a.act, a.M, st, slab);
-            hipLaunchKernelGGL(k_goal_tick, dim3(wgs), dim3(256), 0, st,
-                               a, t);
+            launch(k_goal_tick, wgs, 256, 0, st, a, t);
         }
-        hipLaunchKernelGGL(k_goal_count, dim3(wgs), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_goal_scan, dim3(1), dim3(GOAL_SCAN_THREADS), 0,
-                           st, a);
+        launch(k_goal_count, wgs, 256, 0, st, a);
+        launch(k_goal_scan, 1, GOAL_SCAN_THREADS, 0, st, a);
         // one wave per env, four to a workgroup
         int ewgs = ceil_div(a.M, 4);
-        hipLaunchKernelGGL(k_goal_emit, dim3(ewgs > 2048 ? 2048 : ewgs),
-                           dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_goal_end, dim3(1), dim3(64), 0, st, a);
+        launch(k_goal_emit, ewgs > 2048 ? 2048 : ewgs, 256, 0, st, a);
+        launch(k_goal_end, 1, 64, 0, st, a);
     }
 
     // Totals over the episodes of one goal_rollout_run call, read from the
@@ -1499,12 +1375,8 @@ public:
             throw std::runtime_error("goal_rollout_set_state: bad M");
         const int D = goal_.D;
         const long MD = (long)M * D;
-        std::vector<float> obs(2 * MD), ou(MD, goal_.ou_mu);
-        for (int i = 0; i < M; ++i)
-            for (int k = 0; k < D; ++k) {
-                obs[(long)i * 2 * D + k] = pos[(long)i * D + k];
-                obs[(long)i * 2 * D + D + k] = goal[(long)i * D + k];
-            }
+        std::vector<float> obs = goal_obs(pos, goal, M, D),
+                           ou(MD, goal_.ou_mu);
         std::vector<int> alive(M, 1);
         HIP_CHECK(hipMemcpy(goal_.pos, pos, MD * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(goal_.goal, goal, MD * 4, hipMemcpyHostToDevice));
@@ -1548,12 +1420,12 @@ public:
         const long MO = (long)M * O, MA = (long)M * A;
         const long n_dyn = (long)(O + A) * O;
         float* dyn = nullptr;
-        roll_pool_build(a, [&](auto& sub) {
-            sub(a.obs, MO); sub(a.act, MA); sub(a.act_env, MA); sub(a.z, MO);
-            sub(a.ou_x, MA);
-            sub(a.s_ring, nsteps * MO); sub(a.a_ring, nsteps * MA);
-            sub(a.r_ring, (long)nsteps * M);
-            sub(dyn, n_dyn + O);
+        roll_pool_build(a, [&](DevicePool& p) {
+            p.take(a.obs, MO); p.take(a.act, MA); p.take(a.act_env, MA);
+            p.take(a.z, MO); p.take(a.ou_x, MA);
+            p.take(a.s_ring, nsteps * MO); p.take(a.a_ring, nsteps * MA);
+            p.take(a.r_ring, (long)nsteps * M);
+            p.take(dyn, n_dyn + O);
         });
         // [W; U] then the zero bias the clear left
         HIP_CHECK(hipMemcpy(dyn, W, (long)O * O * 4, hipMemcpyHostToDevice));
@@ -1573,27 +1445,22 @@ public:
         // one wave per env, four to a workgroup
         int twgs = ceil_div(a.M, 4);
         if (twgs > 2048) twgs = 2048;
-        if (reset)
-            hipLaunchKernelGGL(k_syn_reset, dim3(wgs), dim3(256), 0, st,
-                               a);
+        if (reset) launch(k_syn_reset, wgs, 256, 0, st, a);
         FwdJob mix = fwd_job(a.obs, a.act_env, syn_dyn_, syn_dyn_desc_, a.z,
                              ACT_NONE, a.M);
         int emit_k = 0;
         for (int t = 0; t < a.horizon; ++t) {
             roll_fwd_chain(a.obs, a.act, a.M, st, slab);
             int slot = t % a.n;
-            hipLaunchKernelGGL(k_syn_act, dim3(wgs), dim3(256), 0, st, a,
-                               t, slot);
+            launch(k_syn_act, wgs, 256, 0, st, a, t, slot);
             if (fwd_uses_mfma(a.M)) launch_fwd_mfma(mix, false, st);
             else launch_fwd_valu(mix, st);
             int ek = (t >= a.n - 1) ? emit_k : -1;
             int done = (t == a.horizon - 1) ? 1 : 0;
-            hipLaunchKernelGGL(k_syn_tick, dim3(twgs), dim3(256), 0, st,
-                               a, t, slot, ek, done);
+            launch(k_syn_tick, twgs, 256, 0, st, a, t, slot, ek, done);
             if (ek >= 0) ++emit_k;
         }
-        hipLaunchKernelGGL(k_roll_end, dim3(1), dim3(64), 0, st,
-                           (RollCore&)a, (long)emit_k * a.M);
+        launch(k_roll_end, 1, 64, 0, st, a, (long)emit_k * a.M);
     }
 
     void synth_rollout_run(int episodes, bool reset, bool use_graph) {
@@ -1623,18 +1490,15 @@ public:
     // eval_alloc.  rollout_free(), and with it every *_rollout_alloc, drops
     // the evaluation: it models the producer that was allocated.
     EvalArgs eval_{};
-    void* eval_pool_ = nullptr;
+    DevicePool eval_pool_;
     float *e_h1 = nullptr, *e_h2 = nullptr, *e_h3 = nullptr;
-    hipGraph_t eval_graph = nullptr;
-    hipGraphExec_t eval_graph_exec = nullptr;
+    GraphSlot eval_graph_;              // one episode, reset included
     // eval_set_state ran: the next episode starts from what it injected
     bool eval_injected_ = false;
 
     void eval_free() {
-        if (eval_graph_exec) { hipGraphExecDestroy(eval_graph_exec);
-                               eval_graph_exec = nullptr; }
-        if (eval_graph) { hipGraphDestroy(eval_graph); eval_graph = nullptr; }
-        if (eval_pool_) { hipFree(eval_pool_); eval_pool_ = nullptr; }
+        eval_graph_.reset();
+        eval_pool_.reset();
         eval_injected_ = false;
     }
 
@@ -1667,33 +1531,21 @@ public:
         } else if (roll_kind_ == ROLL_SYNTH) {
             a.act_high = syn_.act_high; a.proc_sigma = syn_.proc_sigma;
         }
-        char* base = nullptr;
-        long off = 0;
-        auto sub = [&](auto*& p, long nelem) {      // nelem in 4-byte words
-            if (base) p = reinterpret_cast<decltype(+p)>(base + off);
-            off += (nelem * 4 + 255) & ~255L;
-        };
-        auto carve_all = [&] {
-            off = 0;
-            sub(a.obs, (long)E * O); sub(a.act, (long)E * A);
-            sub(a.ret, 2L * E); sub(a.len, E); sub(a.succ, E);
-            sub(a.words, 2L * (EVAL_WORDS + 1));
+        eval_pool_.build([&](DevicePool& p) {
+            p.take(a.obs, (long)E * O); p.take(a.act, (long)E * A);
+            p.take(a.ret, E); p.take(a.len, E); p.take(a.succ, E);
+            p.take(a.words, EVAL_WORDS + 1);
             if (roll_kind_ == ROLL_PENDULUM) {
-                sub(a.th, E); sub(a.thdot, E);
+                p.take(a.th, E); p.take(a.thdot, E);
             } else if (roll_kind_ == ROLL_GOAL) {
-                sub(a.pos, (long)E * A); sub(a.goal, (long)E * A);
-                sub(a.alive, E);
+                p.take(a.pos, (long)E * A); p.take(a.goal, (long)E * A);
+                p.take(a.alive, E);
             } else {
-                sub(a.act_env, (long)E * A); sub(a.z, (long)E * O);
+                p.take(a.act_env, (long)E * A); p.take(a.z, (long)E * O);
             }
             const long EH = (long)E * cfg.hidden;
-            sub(e_h1, EH); sub(e_h2, EH); sub(e_h3, EH);
-        };
-        carve_all();
-        HIP_CHECK(hipMalloc(&eval_pool_, off));
-        HIP_CHECK(hipMemset(eval_pool_, 0, off));
-        base = (char*)eval_pool_;
-        carve_all();
+            p.take(e_h1, EH); p.take(e_h2, EH); p.take(e_h3, EH);
+        });
         // every episode of a fixed-starts evaluation is episode 1; otherwise
         // k_eval_begin moves 0 on to 1 before the first one
         const long long epoch0 = fixed_starts ? 1 : 0;
@@ -1707,28 +1559,20 @@ public:
         EvalArgs& a = eval_;
         const int E = a.E;
         int wgs = ceil_div(E, 256);
-        hipLaunchKernelGGL(k_eval_begin, dim3(1), dim3(64), 0, stream, a);
+        launch(k_eval_begin, 1, 64, 0, stream, a);
         auto chain = [&] {
             roll_fwd_chain(a.obs, a.act, E, e_h1, e_h2, e_h3, stream,
                            ws.p_actor);
         };
-        if (roll_kind_ == ROLL_PENDULUM) {
+        if (roll_kind_ != ROLL_SYNTH) {
+            const bool pend = roll_kind_ == ROLL_PENDULUM;
             if (reset)
-                hipLaunchKernelGGL(k_eval_pend_reset, dim3(wgs), dim3(256), 0,
-                                   stream, a);
+                launch(pend ? k_eval_pend_reset : k_eval_goal_reset, wgs, 256,
+                       0, stream, a);
             for (int t = 0; t < a.horizon; ++t) {
                 chain();
-                hipLaunchKernelGGL(k_eval_pend_tick, dim3(wgs), dim3(256), 0,
-                                   stream, a, t);
-            }
-        } else if (roll_kind_ == ROLL_GOAL) {
-            if (reset)
-                hipLaunchKernelGGL(k_eval_goal_reset, dim3(wgs), dim3(256), 0,
-                                   stream, a);
-            for (int t = 0; t < a.horizon; ++t) {
-                chain();
-                hipLaunchKernelGGL(k_eval_goal_tick, dim3(wgs), dim3(256), 0,
-                                   stream, a, t);
+                launch(pend ? k_eval_pend_tick : k_eval_goal_tick, wgs, 256,
+                       0, stream, a, t);
             }
         } else {
             const long elems = (long)E * (a.O > a.A ? a.O : a.A);
@@ -1736,23 +1580,18 @@ public:
             if (ewgs > 2048) ewgs = 2048;
             int twgs = ceil_div(E, 4);          // one wave per env
             if (twgs > 2048) twgs = 2048;
-            if (reset)
-                hipLaunchKernelGGL(k_eval_syn_reset, dim3(ewgs), dim3(256), 0,
-                                   stream, a);
+            if (reset) launch(k_eval_syn_reset, ewgs, 256, 0, stream, a);
             FwdJob mix = fwd_job(a.obs, a.act_env, syn_dyn_, syn_dyn_desc_,
                                  a.z, ACT_NONE, E);
             for (int t = 0; t < a.horizon; ++t) {
                 chain();
-                hipLaunchKernelGGL(k_eval_syn_act, dim3(ewgs), dim3(256), 0,
-                                   stream, a);
+                launch(k_eval_syn_act, ewgs, 256, 0, stream, a);
                 if (fwd_uses_mfma(E)) launch_fwd_mfma(mix);
                 else launch_fwd_valu(mix);
-                hipLaunchKernelGGL(k_eval_syn_tick, dim3(twgs), dim3(256), 0,
-                                   stream, a, t);
+                launch(k_eval_syn_tick, twgs, 256, 0, stream, a, t);
             }
         }
-        hipLaunchKernelGGL(k_eval_reduce, dim3(1),
-                           dim3(EVAL_REDUCE_THREADS), 0, stream, a);
+        launch(k_eval_reduce, 1, EVAL_REDUCE_THREADS, 0, stream, a);
     }
 
     // `episodes` evaluation episodes; the result words sum over them
@@ -1768,16 +1607,9 @@ public:
                 eval_injected_ = false;
                 eval_enqueue_episode(false);
             } else if (use_graph) {
-                if (!eval_graph_exec) {
-                    HIP_CHECK(hipStreamBeginCapture(
-                        stream, hipStreamCaptureModeThreadLocal));
-                    eval_enqueue_episode(true);
-                    HIP_CHECK(hipStreamEndCapture(stream, &eval_graph));
-                    HIP_CHECK(hipGraphInstantiate(&eval_graph_exec,
-                                                  eval_graph, nullptr,
-                                                  nullptr, 0));
-                }
-                HIP_CHECK(hipGraphLaunch(eval_graph_exec, stream));
+                eval_graph_.ensure(stream,
+                                   [&] { eval_enqueue_episode(true); });
+                eval_graph_.launch(stream);
             } else {
                 eval_enqueue_episode(true);
             }
@@ -1823,27 +1655,15 @@ public:
         if (roll_kind_ == ROLL_PENDULUM) {
             if (nx != E || ny != E)
                 throw std::runtime_error("eval_set_state: th/thdot not [E]");
-            std::vector<float> obs(3 * E);
-            for (long i = 0; i < E; ++i) {
-                obs[i * 3 + 0] = cosf(x[i]);
-                obs[i * 3 + 1] = sinf(x[i]);
-                obs[i * 3 + 2] = y[i];
-            }
             up(a.th, x, E * 4); up(a.thdot, y, E * 4);
-            up(a.obs, obs.data(), 3 * E * 4);
+            up(a.obs, pendulum_obs(x, y, E).data(), 3 * E * 4);
         } else if (roll_kind_ == ROLL_GOAL) {
             const long D = a.D, ED = E * D;
             if (nx != ED || ny != ED)
                 throw std::runtime_error("eval_set_state: pos/goal not [E][D]");
-            std::vector<float> obs(2 * ED);
-            for (long i = 0; i < E; ++i)
-                for (long k = 0; k < D; ++k) {
-                    obs[i * 2 * D + k] = x[i * D + k];
-                    obs[i * 2 * D + D + k] = y[i * D + k];
-                }
             std::vector<int> alive(E, 1);
             up(a.pos, x, ED * 4); up(a.goal, y, ED * 4);
-            up(a.obs, obs.data(), 2 * ED * 4);
+            up(a.obs, goal_obs(x, y, E, D).data(), 2 * ED * 4);
             up(a.alive, alive.data(), E * 4);
         } else {
             if (nx != E * a.O)

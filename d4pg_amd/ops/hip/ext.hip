@@ -62,21 +62,18 @@ static py::dict info(int64_t h) {
     d["seed"] = (int64_t)e.cfg.seed;
     // episodes one collection window can hold; 0 before collect_alloc
     d["collect_max_episodes"] = e.collect_max_episodes_;
-    py::list al, cl;
-    for (int i = 0; i < 4; ++i) {
-        py::dict ld;
-        ld["in1"] = e.anet.l[i].in1; ld["in2"] = e.anet.l[i].in2;
-        ld["out"] = e.anet.l[i].out; ld["w_off"] = e.anet.l[i].w_off;
-        ld["b_off"] = e.anet.l[i].b_off;
-        al.append(ld);
-        py::dict ld2;
-        ld2["in1"] = e.cnet.l[i].in1; ld2["in2"] = e.cnet.l[i].in2;
-        ld2["out"] = e.cnet.l[i].out; ld2["w_off"] = e.cnet.l[i].w_off;
-        ld2["b_off"] = e.cnet.l[i].b_off;
-        cl.append(ld2);
-    }
-    d["actor_layers"] = al;
-    d["critic_layers"] = cl;
+    auto layers = [](const Net& net) {
+        py::list out;
+        for (const LayerDesc& l : net.l) {
+            py::dict ld;
+            ld["in1"] = l.in1; ld["in2"] = l.in2; ld["out"] = l.out;
+            ld["w_off"] = l.w_off; ld["b_off"] = l.b_off;
+            out.append(ld);
+        }
+        return out;
+    };
+    d["actor_layers"] = layers(e.anet);
+    d["critic_layers"] = layers(e.cnet);
     return d;
 }
 
@@ -608,97 +605,87 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
         if (c.beta_t > 0 && ((c.beta_t - 1) & 1))
             name = "bs_b";
     }
-    struct Ent { const void* p; std::vector<long> shape; bool is_long; bool is_double; };
-    std::unordered_map<std::string, Ent> m = {
-        {"bs", {e.ws.bs, {B, O}, false, false}},
-        {"bs_b", {e.ws.bs_b, {B, O}, false, false}},
-        {"ba", {e.ws.ba, {B, A}, false, false}},
-        {"br", {e.ws.br, {B}, false, false}},
-        {"bs2", {e.ws.bs2, {B, O}, false, false}},
-        {"bd", {e.ws.bd, {B}, false, false}},
-        {"bw", {e.ws.bw, {B}, false, false}},
-        {"pri", {e.ws.pri, {B}, false, false}},
-        {"bidx", {e.ws.bidx, {B}, true, false}},
-        {"a2", {e.ws.a2, {B, A}, false, false}},
-        {"p_t", {e.ws.p_t, {B, K}, false, false}},
-        {"m_proj", {e.ws.m_proj, {B, K}, false, false}},
-        {"q", {e.ws.q, {B, K}, false, false}},
-        {"pq", {e.ws.pq, {B, K}, false, false}},
-        {"a_out", {e.ws.a_out, {B, A}, false, false}},
-        {"dlog", {e.ws.dlog, {B, K}, false, false}},
-        {"c_h1", {e.ws.c_h1, {B, H}, false, false}},
-        {"c_h2", {e.ws.c_h2, {B, H}, false, false}},
-        {"c_h3", {e.ws.c_h3, {B, H}, false, false}},
-        {"at_h1", {e.ws.at_h1, {B, H}, false, false}},
+    const auto i64 = torch::kInt64, f64 = torch::kFloat64;
+    struct Ent {
+        const char* name;
+        const void* p;
+        std::vector<long> shape;
+        torch::ScalarType dtype = torch::kFloat32;
+    };
+    std::vector<Ent> tab = {
+        {"bs", e.ws.bs, {B, O}},
+        {"bs_b", e.ws.bs_b, {B, O}},
+        {"ba", e.ws.ba, {B, A}},
+        {"br", e.ws.br, {B}},
+        {"bs2", e.ws.bs2, {B, O}},
+        {"bd", e.ws.bd, {B}},
+        {"bw", e.ws.bw, {B}},
+        {"pri", e.ws.pri, {B}},
+        {"bidx", e.ws.bidx, {B}, i64},
+        {"a2", e.ws.a2, {B, A}},
+        {"p_t", e.ws.p_t, {B, K}},
+        {"m_proj", e.ws.m_proj, {B, K}},
+        {"q", e.ws.q, {B, K}},
+        {"pq", e.ws.pq, {B, K}},
+        {"a_out", e.ws.a_out, {B, A}},
+        {"dlog", e.ws.dlog, {B, K}},
+        {"c_h1", e.ws.c_h1, {B, H}},
+        {"c_h2", e.ws.c_h2, {B, H}},
+        {"c_h3", e.ws.c_h3, {B, H}},
+        {"at_h1", e.ws.at_h1, {B, H}},
         // the wide step's remaining GEMM inputs and outputs (per-GEMM
         // tests, tests/test_gpu_wide_bf16.py)
-        {"at_h2", {e.ws.at_h2, {B, H}, false, false}},
-        {"at_h3", {e.ws.at_h3, {B, H}, false, false}},
-        {"ct_h1", {e.ws.ct_h1, {B, H}, false, false}},
-        {"ct_h2", {e.ws.ct_h2, {B, H}, false, false}},
-        {"ct_h3", {e.ws.ct_h3, {B, H}, false, false}},
-        {"d1", {e.ws.d1, {B, H}, false, false}},
-        {"d2", {e.ws.d2, {B, H}, false, false}},
-        {"d3", {e.ws.d3, {B, H}, false, false}},
-        {"pa_h1", {e.ws.pa_h1, {B, H}, false, false}},
-        {"pa_h2", {e.ws.pa_h2, {B, H}, false, false}},
-        {"pa_h3", {e.ws.pa_h3, {B, H}, false, false}},
-        {"pc_h1", {e.ws.pc_h1, {B, H}, false, false}},
-        {"pc_h2", {e.ws.pc_h2, {B, H}, false, false}},
-        {"pc_h3", {e.ws.pc_h3, {B, H}, false, false}},
-        {"pd3", {e.ws.pd3, {B, K}, false, false}},
-        {"pd2", {e.ws.pd2, {B, H}, false, false}},
-        {"pdh1", {e.ws.pdh1, {B, H}, false, false}},
-        {"pda", {e.ws.pda, {B, A}, false, false}},
-        {"adz", {e.ws.adz, {B, A}, false, false}},
-        {"az1", {e.ws.az1, {B, H}, false, false}},
-        {"az2", {e.ws.az2, {B, H}, false, false}},
-        {"az3", {e.ws.az3, {B, H}, false, false}},
-        {"tstamp", {e.ws.tstamp, {64}, true, false}},
-        {"sum_tree", {e.ws.sum_tree, {2 * e.ws.tree_cap}, false, true}},
-        {"min_tree", {e.ws.min_tree, {2 * e.ws.tree_cap}, false, true}},
+        {"at_h2", e.ws.at_h2, {B, H}},
+        {"at_h3", e.ws.at_h3, {B, H}},
+        {"ct_h1", e.ws.ct_h1, {B, H}},
+        {"ct_h2", e.ws.ct_h2, {B, H}},
+        {"ct_h3", e.ws.ct_h3, {B, H}},
+        {"d1", e.ws.d1, {B, H}},
+        {"d2", e.ws.d2, {B, H}},
+        {"d3", e.ws.d3, {B, H}},
+        {"pa_h1", e.ws.pa_h1, {B, H}},
+        {"pa_h2", e.ws.pa_h2, {B, H}},
+        {"pa_h3", e.ws.pa_h3, {B, H}},
+        {"pc_h1", e.ws.pc_h1, {B, H}},
+        {"pc_h2", e.ws.pc_h2, {B, H}},
+        {"pc_h3", e.ws.pc_h3, {B, H}},
+        {"pd3", e.ws.pd3, {B, K}},
+        {"pd2", e.ws.pd2, {B, H}},
+        {"pdh1", e.ws.pdh1, {B, H}},
+        {"pda", e.ws.pda, {B, A}},
+        {"adz", e.ws.adz, {B, A}},
+        {"az1", e.ws.az1, {B, H}},
+        {"az2", e.ws.az2, {B, H}},
+        {"az3", e.ws.az3, {B, H}},
+        {"tstamp", e.ws.tstamp, {64}, i64},
+        {"sum_tree", e.ws.sum_tree, {2 * e.ws.tree_cap}, f64},
+        {"min_tree", e.ws.min_tree, {2 * e.ws.tree_cap}, f64},
         // per-chunk sums of squares of the gradient slabs (clipping on)
-        {"gn_part_actor",
-         {e.ws.gn_part_a, {gn_chunks(e.anet.n_params)}, false, true}},
-        {"gn_part_critic",
-         {e.ws.gn_part_c, {gn_chunks(e.cnet.n_params)}, false, true}},
+        {"gn_part_actor", e.ws.gn_part_a, {gn_chunks(e.anet.n_params)}, f64},
+        {"gn_part_critic", e.ws.gn_part_c, {gn_chunks(e.cnet.n_params)}, f64},
     };
     if (e.stage_pool_) {
         // the actor snapshot and the staging store of an overlapped
         // collection (whole store; rows past the staged count are stale)
         const long S = e.stage_rows_;
-        m.insert({{"p_actor_roll",
-                   {e.p_actor_roll, {e.anet.n_params}, false, false}},
-                  {"stage_s", {e.st_rs, {S, O}, false, false}},
-                  {"stage_a", {e.st_ra, {S, A}, false, false}},
-                  {"stage_r", {e.st_rr, {S}, false, false}},
-                  {"stage_s2", {e.st_rs2, {S, O}, false, false}},
-                  {"stage_d", {e.st_rd, {S}, false, false}}});
+        tab.insert(tab.end(),
+                   {{"p_actor_roll", e.p_actor_roll, {e.anet.n_params}},
+                    {"stage_s", e.st_rs, {S, O}},
+                    {"stage_a", e.st_ra, {S, A}},
+                    {"stage_r", e.st_rr, {S}},
+                    {"stage_s2", e.st_rs2, {S, O}},
+                    {"stage_d", e.st_rd, {S}}});
     }
-    auto it = m.find(name);
-    if (it == m.end()) throw std::runtime_error("unknown buffer " + name);
-    auto& ent = it->second;
-    long n = 1;
-    for (long s : ent.shape) n *= s;
-    torch::Tensor out;
-    if (n == 0) {                       // the trees of a uniform engine
-        out = torch::empty(ent.shape, ent.is_long ? torch::kInt64
-                           : ent.is_double ? torch::kFloat64
-                                           : torch::kFloat32);
-    } else if (ent.is_long) {
-        out = torch::empty(ent.shape, torch::kInt64);
-        HIP_CHECK(hipMemcpy(out.data_ptr<int64_t>(), ent.p, n * 8,
-                            hipMemcpyDeviceToHost));
-    } else if (ent.is_double) {
-        out = torch::empty(ent.shape, torch::kFloat64);
-        HIP_CHECK(hipMemcpy(out.data_ptr<double>(), ent.p, n * 8,
-                            hipMemcpyDeviceToHost));
-    } else {
-        out = torch::empty(ent.shape, torch::kFloat32);
-        HIP_CHECK(hipMemcpy(out.data_ptr<float>(), ent.p, n * 4,
-                            hipMemcpyDeviceToHost));
+    for (const Ent& ent : tab) {
+        if (name != ent.name) continue;
+        auto out = torch::empty(ent.shape, ent.dtype);
+        if (out.numel())                // zero: the trees of a uniform engine
+            HIP_CHECK(hipMemcpy(out.data_ptr(), ent.p,
+                                out.numel() * out.element_size(),
+                                hipMemcpyDeviceToHost));
+        return out;
     }
-    return out;
+    throw std::runtime_error("unknown buffer " + name);
 }
 
 }  // namespace d4pg
