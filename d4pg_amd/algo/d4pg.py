@@ -44,6 +44,7 @@ from ..replay.uniform import Replay
 from ..replay.per import PrioritizedReplayBuffer
 from ..replay.schedules import LinearSchedule
 from .projection import categorical_projection
+from .quantile import quantile_huber_loss, quantile_targets
 
 
 class DDPG:
@@ -86,12 +87,25 @@ class DDPG:
             critic_dist_info = {"type": "categorical", "v_min": -100.0,
                                 "v_max": 100.0, "n_atoms": 51}
         self.dist_type = critic_dist_info["type"]
-        if self.dist_type != "categorical":
+        if self.dist_type not in ("categorical", "quantile"):
             raise NotImplementedError(
                 "unsupported critic distribution type %r" % self.dist_type)
+        self.n_atoms = int(critic_dist_info["n_atoms"])
+        # quantile head: n_atoms is the quantile count, there is no support
+        # (v_min / v_max are accepted and ignored: pinned to one fixed pair so
+        # that nothing downstream can depend on them) and kappa is the Huber
+        # threshold.  true_td_priorities is accepted and has no effect: the
+        # <m, q> proxy has no meaning without a support, and both values
+        # give the priority |mean_j T_j - mean_i theta_i| + eps.
+        self.kappa = float(critic_dist_info.get("kappa", 1.0))
+        if not self.kappa > 0.0:
+            raise ValueError("huber kappa must be > 0, got %r" % self.kappa)
+        if self.dist_type == "quantile":
+            critic_dist_info = {"type": "quantile", "n_atoms": self.n_atoms,
+                                "kappa": self.kappa,
+                                "v_min": 0.0, "v_max": 1.0}
         self.v_min = float(critic_dist_info["v_min"])
         self.v_max = float(critic_dist_info["v_max"])
-        self.n_atoms = int(critic_dist_info["n_atoms"])
         self.delta = (self.v_max - self.v_min) / float(self.n_atoms - 1)
         # column vector like the reference (ddpg.py:47) for matmul parity
         self.bin_centers = np.arange(self.n_atoms, dtype=np.float64) \
@@ -264,14 +278,22 @@ class DDPG:
         s2 = torch.as_tensor(np.asarray(next_states, dtype=np.float32), device=dev)
         d = torch.as_tensor(np.asarray(terminates, dtype=np.float32), device=dev)
 
+        quantile = self.dist_type == "quantile"
+
         # -- critic update --
         with torch.no_grad():
             a2 = self.actor_target(s2)
             target_dist = self.critic_target(s2, a2)
-            m = categorical_projection(target_dist, r, d, self.v_min,
-                                       self.v_max, self.n_step_gamma)
+            if quantile:
+                m = quantile_targets(target_dist, r, d, self.n_step_gamma)
+            else:
+                m = categorical_projection(target_dist, r, d, self.v_min,
+                                           self.v_max, self.n_step_gamma)
         q_dist = self.critic(s, a)
-        per_sample_ce = -(m * torch.log(q_dist + 1e-10)).sum(dim=1)
+        if quantile:
+            per_sample_ce = quantile_huber_loss(q_dist, m, self.kappa)
+        else:
+            per_sample_ce = -(m * torch.log(q_dist + 1e-10)).sum(dim=1)
         if self.is_weighting and weights is not None:
             w = torch.as_tensor(np.asarray(weights, dtype=np.float32),
                                 device=dev)
@@ -281,7 +303,9 @@ class DDPG:
 
         td_errors = None
         if self.prioritized_replay:
-            if self.true_td_priorities:
+            if quantile:
+                td_errors = m.mean(dim=1) - q_dist.detach().mean(dim=1)
+            elif self.true_td_priorities:
                 exp_q = (q_dist.detach() * self._z).sum(dim=1)
                 exp_m = (m * self._z).sum(dim=1)
                 td_errors = exp_m - exp_q
@@ -306,7 +330,10 @@ class DDPG:
         # -- actor update --
         z = self._z.reshape(-1, 1)
         policy_q = self.critic(s, self.actor(s))
-        policy_loss = -(policy_q.matmul(z)).mean()
+        if quantile:
+            policy_loss = -policy_q.mean(dim=1).mean()
+        else:
+            policy_loss = -(policy_q.matmul(z)).mean()
         self.actor.zero_grad()
         if global_model is not None:
             global_model.actor.zero_grad()
@@ -404,6 +431,9 @@ class DDPG:
                 "seed": eng.info()["seed"],
                 # replay mode: a checkpoint loads only into the same mode
                 "prioritized": bool(eng.info()["prioritized"]),
+                # critic head: a checkpoint loads only into the same kind
+                "dist": str(eng.info()["dist"]),
+                "kappa": float(eng.info()["kappa"]),
             }
         # nn.Module.state_dict() returns REFERENCES to the live tensors —
         # continued training would silently mutate the checkpoint.  A
@@ -416,6 +446,14 @@ class DDPG:
         # build the fused bridge FIRST: the on-HBM replay blob and engine
         # slabs in `st` have nowhere to land otherwise, and the CPU replay
         # buffer cannot parse the GPU-format replay dict.
+        ckpt_dist = st.get("engine", {}).get("dist", "categorical")
+        if "engine" in st and ckpt_dist != self.dist_type:
+            raise ValueError(
+                "checkpoint critic head (%s) does not match this agent's "
+                "(%s) — the two heads read the same fc3 outputs differently "
+                "and there is no conversion; build the agent with "
+                "critic_dist_info type %r"
+                % (ckpt_dist, self.dist_type, ckpt_dist))
         if self.backend == "hip" and "engine" in st and self._fused is None:
             from ..ops import build_fused_engine
             self._fused = build_fused_engine(self)

@@ -28,6 +28,17 @@ def check_gemm_precision(value) -> None:
                          % (GEMM_PRECISIONS, value))
 
 
+CRITIC_DISTS = ("categorical", "quantile")
+
+
+def _positive_float(text: str) -> float:
+    """argparse type of --huber_kappa: a float > 0 (NaN refused)."""
+    value = float(text)
+    if not value > 0.0:
+        raise argparse.ArgumentTypeError("must be > 0, got %r" % text)
+    return value
+
+
 def make_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="MI355X-native D4PG")
 
@@ -56,7 +67,19 @@ def make_parser() -> argparse.ArgumentParser:
                    help="C51 distribution support minimum")
     p.add_argument("--v_max", default=100.0, type=float,
                    help="C51 distribution support maximum")
-    p.add_argument("--n_atoms", default=51, type=int, help="C51 atom count")
+    p.add_argument("--n_atoms", default=51, type=int,
+                   help="C51 atom count; with --critic_dist quantile the "
+                        "number of quantiles")
+    p.add_argument("--critic_dist", default="categorical", type=str,
+                   choices=list(CRITIC_DISTS),
+                   help="critic head: 'categorical' is C51 on the support "
+                        "[--v_min, --v_max]; 'quantile' is quantile "
+                        "regression with --n_atoms quantiles and no support "
+                        "(--v_min / --v_max are then ignored), on both "
+                        "backends")
+    p.add_argument("--huber_kappa", default=1.0, type=_positive_float,
+                   help="Huber threshold of the quantile critic's loss, > 0 "
+                        "(ignored by the categorical head)")
     p.add_argument("--multithread", default=0, type=int,
                    help="1 = spawn parallel workers + evaluator")
     p.add_argument("--n_steps", default=1, type=int, help="n-step return horizon")
@@ -175,13 +198,18 @@ def noise_kwargs(args) -> dict:
 
 
 def critic_dist_info(args) -> dict:
-    """The derived distributional-critic config dict (main.py:373-376 parity)."""
-    return {
-        "type": "categorical",
+    """The derived distributional-critic config dict (main.py:373-376 parity).
+    --critic_dist quantile adds the Huber threshold; v_min / v_max ride along
+    and are ignored by that head."""
+    info = {
+        "type": getattr(args, "critic_dist", "categorical"),
         "v_min": args.v_min,
         "v_max": args.v_max,
         "n_atoms": args.n_atoms,
     }
+    if info["type"] == "quantile":
+        info["kappa"] = float(getattr(args, "huber_kappa", 1.0))
+    return info
 
 
 def run_dir_name(args) -> str:
@@ -237,6 +265,8 @@ class D4PGConfig:
     vector_envs: int = 0
     gpu_actors: int = -1
     her_ratio: float = 0.8
+    critic_dist: str = "categorical"
+    huber_kappa: float = 1.0
     gemm_precision: str = "fp32"
     async_collect: int = 0
     clip_grad_norm: float = 0.0

@@ -78,14 +78,23 @@ class critic(nn.Module):
     (the 'mixture_of_gaussian' head the reference declares but never
     implements, models.py:63-65, is rejected here with a clear error instead
     of silently passing).
+
+    ``{'type': 'quantile', 'n_atoms': K, 'kappa': 1.0}`` gives the
+    quantile-regression head: same layers, keys and shapes, but forward
+    returns the raw fc3 output, the values of the K fixed quantiles
+    tau_i = (2i + 1) / (2K) (algo/quantile.py).  v_min / v_max are accepted
+    and ignored; ``log=True`` has no meaning there and is refused.
     """
+
+    DIST_TYPES = ("categorical", "quantile")
 
     def __init__(self, state_size: int, action_size: int, dist_info: dict,
                  hidden: int = 256):
         super().__init__()
-        if dist_info.get("type", "categorical") != "categorical":
+        self.dist_type = dist_info.get("type", "categorical")
+        if self.dist_type not in self.DIST_TYPES:
             raise NotImplementedError(
-                "only the categorical (C51) critic head exists; "
+                "only the categorical (C51) and quantile critic heads exist; "
                 "'%s' is not implemented" % dist_info.get("type"))
         self.state_size = state_size
         self.action_size = action_size
@@ -111,6 +120,11 @@ class critic(nn.Module):
         h = F.relu(self.fc2(torch.cat([h, action], dim=-1)))
         h = F.relu(self.fc2_2(h))
         logits = self.fc3(h)
+        if self.dist_type == "quantile":
+            if log:
+                raise ValueError("the quantile head returns quantile values, "
+                                 "not probabilities: log=True has no meaning")
+            return logits
         if log:
             return F.log_softmax(logits, dim=-1)
         return F.softmax(logits, dim=-1)

@@ -183,7 +183,8 @@ class FusedEngine:
                  per_alpha=0.6, per_beta0=0.4, per_beta_iters=100000,
                  per_eps=1e-6, seed=0, is_weighting=False,
                  prioritized=True, true_td_priorities=False,
-                 gemm_precision="fp32", max_grad_norm=0.0):
+                 gemm_precision="fp32", max_grad_norm=0.0,
+                 dist="categorical", kappa=1.0):
         """prioritized=False: uniform replay (an integer philox draw per
         probe, IS weights exactly 1, no sum/min trees allocated or
         maintained).  true_td_priorities: the written-back priority is
@@ -198,7 +199,14 @@ class FusedEngine:
         critic separately, on all three train paths; Adam consumes the
         scaled gradient while g_actor / g_critic keep the raw one
         (ARCHITECTURE.md, "Gradient clipping").  0 is off; the engine
-        refuses a negative or NaN threshold."""
+        refuses a negative or NaN threshold.  dist="quantile": the
+        quantile-regression critic head on all three train paths — n_atoms
+        quantiles at tau_i = (2i + 1) / (2 n_atoms), identity heads,
+        quantile-Huber loss with threshold kappa > 0, priorities
+        |mean T - mean theta| + per_eps whatever true_td_priorities says;
+        v_min / v_max are unread (ARCHITECTURE.md, "Quantile critic").  The
+        engine refuses an unknown dist and a kappa that is <= 0 or NaN; the
+        categorical engine ignores kappa."""
         check_gemm_precision(gemm_precision)
         self.ext = load_extension()
         self.h = self.ext.create(
@@ -208,7 +216,9 @@ class FusedEngine:
             float(per_beta0), int(per_beta_iters), float(per_eps),
             int(seed), bool(is_weighting), bool(prioritized),
             bool(true_td_priorities), gemm_precision == "bf16",
-            float(max_grad_norm))
+            float(max_grad_norm), str(dist), float(kappa))
+        self.dist = str(dist)
+        self.kappa = float(kappa)
         self.batch = batch
         self.max_grad_norm = float(max_grad_norm)
         self.gemm_precision = gemm_precision
@@ -573,6 +583,7 @@ class FusedDDPGBridge:
             true_td_priorities=ddpg.true_td_priorities,
             gemm_precision=ddpg.gemm_precision,
             max_grad_norm=ddpg.max_grad_norm,
+            dist=ddpg.dist_type, kappa=ddpg.kappa,
             seed=0 if ddpg.rng is None else int(ddpg.rng.integers(1 << 31)))
         self.engine.load_from_modules(ddpg.actor, ddpg.actor_target,
                                       ddpg.critic, ddpg.critic_target)

@@ -128,6 +128,11 @@ public:
             throw std::runtime_error("layer fan-in exceeds FWD_XMAX LDS tile");
         if (c.atoms > 64)
             throw std::runtime_error("n_atoms > 64 (softmax is wave-wide)");
+        if (c.dist != DIST_CATEGORICAL && c.dist != DIST_QUANTILE)
+            throw std::runtime_error("unknown critic head (dist)");
+        if (!(c.kappa > 0.f))               // zero, negative or NaN
+            throw std::runtime_error(
+                "kappa (the quantile head's Huber threshold) must be > 0");
         if (c.gemm_bf16 && c.batch <= 512)
             throw std::runtime_error(
                 "gemm_precision='bf16' needs batch > 512: only the wide "
@@ -149,6 +154,7 @@ public:
         ws.prioritized = c.prioritized; ws.true_td = c.true_td;
         ws.seed = c.seed;
         ws.max_grad_norm = c.max_grad_norm;
+        ws.dist = c.dist; ws.kappa = c.kappa;
         ws.tree_cap = has_trees() ? next_pow2(c.capacity) : 0;
         ws.n_actor = anet.n_params; ws.n_critic = cnet.n_params;
         for (int i = 0; i < 4; ++i) {
@@ -165,8 +171,7 @@ public:
         hipDeviceProp_t prop;
         HIP_CHECK(hipGetDeviceProperties(&prop, dev));
         HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, clip() ? k_step_persistent<true>
-                            : k_step_persistent<false>, 256, 0));
+            &per_cu, persistent_kernel(), 256, 0));
         persistent_fits_ = (long)per_cu * prop.multiProcessorCount >= PNWG;
         device_ = dev;
         alloc();
@@ -186,6 +191,24 @@ public:
     // clip-on kernels and launches.  Off, every launch sequence is the
     // plain one.
     bool clip() const { return cfg.max_grad_norm > 0.0; }
+
+    // The quantile critic head is on: the one predicate behind the QR
+    // kernel instantiations and the identity heads.
+    bool quantile() const { return cfg.dist == DIST_QUANTILE; }
+
+    // activation of the three critic-family heads (critic, critic_target,
+    // the policy chain's critic)
+    int head_act() const { return quantile() ? ACT_NONE : ACT_SOFTMAX; }
+
+    // the persistent kernel's instantiation for this engine
+    using PersistentKernel = void (*)(StepArgs, int);
+    PersistentKernel persistent_kernel() const {
+        if (quantile())
+            return clip() ? k_step_persistent<true, true>
+                          : k_step_persistent<false, true>;
+        return clip() ? k_step_persistent<true, false>
+                      : k_step_persistent<false, false>;
+    }
 
     // internal tree nodes from the leaves: one bandwidth-bound sweep per
     // level (bulk ingest, synth_fill, once per rollout episode)
@@ -514,8 +537,7 @@ public:
     }
 
     void enqueue_persistent(int nsteps) {
-        launch(clip() ? k_step_persistent<true> : k_step_persistent<false>,
-               PNWG, 256, 0, stream, ws, nsteps);
+        launch(persistent_kernel(), PNWG, 256, 0, stream, ws, nsteps);
     }
 
     // All four layers' weight gradients of one net in a single k_bwd4
@@ -576,7 +598,9 @@ public:
         long smem = rb_lds_bytes(H);
         if (mask & PH_CRITIC_GRADS) {
             launch_per_sample();
-            launch(k_critic_rowblock, row_wgs, 256, smem, stream, ws);
+            launch(quantile() ? k_critic_rowblock<true>
+                              : k_critic_rowblock<false>,
+                   row_wgs, 256, smem, stream, ws);
             launch_dw4({{ws.d1, ws.bs, nullptr},
                         {ws.d2, ws.c_h1, ws.ba},
                         {ws.d3, ws.c_h2, nullptr},
@@ -585,7 +609,9 @@ public:
         }
         if (mask & PH_CRITIC_APPLY) launch_adam_lerp(false);
         if (mask & PH_ACTOR_GRADS) {
-            launch(k_policy_rowblock, row_wgs, 256, smem, stream, ws);
+            launch(quantile() ? k_policy_rowblock<true>
+                              : k_policy_rowblock<false>,
+                   row_wgs, 256, smem, stream, ws);
             launch_dw4({{ws.az1, ws.bs, nullptr},
                         {ws.az2, ws.pa_h1, nullptr},
                         {ws.az3, ws.pa_h2, nullptr},
@@ -635,20 +661,21 @@ public:
         launch_fwd({fwd_job(ws.at_h3, nullptr, ws.p_actor_t, anet.l[3], ws.a2,
                             ACT_TANH),
                     fwd_job(ws.c_h3, nullptr, ws.p_critic, cnet.l[3], ws.q,
-                            ACT_SOFTMAX)}, bf);
+                            head_act())}, bf);
         // P6-8: c_t.L2(cat ct_h1, a2), c_t.L3, c_t.L4 softmax -> p_t
         launch_fwd({fwd_job(ws.ct_h1, ws.a2, ws.p_critic_t, cnet.l[1], ws.ct_h2,
                             ACT_RELU)}, bf);
         launch_fwd({fwd_job(ws.ct_h2, nullptr, ws.p_critic_t, cnet.l[2],
                             ws.ct_h3, ACT_RELU)}, bf);
         launch_fwd({fwd_job(ws.ct_h3, nullptr, ws.p_critic_t, cnet.l[3], ws.p_t,
-                            ACT_SOFTMAX)}, bf);
+                            head_act())}, bf);
         // P9+P10 fused: projection + CE grad + priorities
-        launch(k_project_ce, min(row_wgs, 256), 256,
+        launch(quantile() ? k_project_ce<true> : k_project_ce<false>,
+               min(row_wgs, 256), 256,
                waves_per_wg * 64 * sizeof(float), stream,
                ws.p_t, ws.br, ws.bd, ws.q, ws.bw, ws.m_proj, ws.dlog, ws.pri,
                ws.cnt, B, K, cfg.v_min, cfg.v_max, cfg.gamma_n, cfg.per_eps,
-               cfg.is_weighting, cfg.true_td);
+               cfg.is_weighting, cfg.true_td, cfg.kappa);
         // P11-14: critic backward L4..L1
         launch_bwd(ws.dlog, ws.c_h3, nullptr, ws.p_critic, ws.g_critic,
                    cnet.l[3], ws.d3, nullptr, ws.c_h3, ACT_RELU, true, bf);
@@ -680,9 +707,10 @@ public:
         launch_fwd({fwd_job(ws.pc_h2, nullptr, ws.p_critic, cnet.l[2], ws.pc_h3,
                             ACT_RELU)}, bf);
         launch_fwd({fwd_job(ws.pc_h3, nullptr, ws.p_critic, cnet.l[3], ws.pq,
-                            ACT_SOFTMAX)}, bf);
+                            head_act())}, bf);
         // P23: policy head gradient
-        launch(k_policy_grad, min(row_wgs, 256), 256, 0, stream, ws.pq,
+        launch(quantile() ? k_policy_grad<true> : k_policy_grad<false>,
+               min(row_wgs, 256), 256, 0, stream, ws.pq,
                ws.pd3, ws.cnt, B, K, cfg.v_min, cfg.v_max);
         // P24-26: dX back through critic' (no dW), ending at da
         launch_bwd(ws.pd3, ws.pc_h3, nullptr, ws.p_critic, nullptr, cnet.l[3],

@@ -72,6 +72,11 @@ struct LayerDesc {
 
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_SOFTMAX = 3 };
 
+// The critic head: C51 probabilities on a fixed support (softmax head,
+// projection, cross-entropy) or the values of K fixed quantiles (identity
+// head, quantile-Huber loss; ARCHITECTURE.md, "Quantile critic").
+enum Dist { DIST_CATEGORICAL = 0, DIST_QUANTILE = 1 };
+
 struct EngineCfg {
     int obs, act, hidden, atoms, batch;
     long capacity;             // replay capacity (will be rounded to pow2 tree)
@@ -85,6 +90,8 @@ struct EngineCfg {
     int gemm_bf16 = 0;         // wide train step: bf16 MFMA operands (RNE),
                                // fp32 accumulate; batch > 512 only
     double max_grad_norm = 0;  // global-norm gradient clip, per net; 0: off
+    int dist = DIST_CATEGORICAL;   // critic head (Dist)
+    float kappa = 1.f;         // quantile head: Huber threshold, > 0
 };
 
 // device-side counters (one small block)
@@ -190,6 +197,11 @@ struct StepArgs {
     double max_grad_norm;
     double *gn_part_a, *gn_part_c;
     GradStats* gstat;
+    // critic head (Dist) and the quantile head's Huber threshold; last, so
+    // every other field keeps its offset.  v_min / v_max are unread under
+    // DIST_QUANTILE
+    int dist;
+    float kappa;
 };
 
 

@@ -74,7 +74,9 @@ __global__ void k_fwd(FwdJob j) {
 // ---- fused C51 projection + CE grad + priorities (wide path) ----------------
 // One wave per row over c51_project_row + ce_grad_row, the formulas the
 // persistent p_project_ce and k_critic_rowblock run too; fusing the two saves
-// a launch + the m round-trip.
+// a launch + the m round-trip.  QR: qr_target_row + qr_grad_row in their
+// place (p_t holds theta', q theta, m_out T), as on the other two paths.
+template <bool QR>
 __global__ void k_project_ce(const float* __restrict__ p_t,
                              const float* __restrict__ r,
                              const float* __restrict__ d,
@@ -85,7 +87,7 @@ __global__ void k_project_ce(const float* __restrict__ p_t,
                              float* __restrict__ pri, Counters* cnt,
                              int B, int K, float v_min, float v_max,
                              float gamma_n, float per_eps,
-                             int is_weighting, int true_td) {
+                             int is_weighting, int true_td, float kappa) {
     int lane = threadIdx.x & 63;
     int wrow = threadIdx.x / 64;
     int wpb = blockDim.x / 64;
@@ -99,6 +101,22 @@ __global__ void k_project_ce(const float* __restrict__ p_t,
     for (int row = blockIdx.x * wpb + wrow; row < B;
          row += gridDim.x * wpb) {
         float p = (lane < K) ? p_t[(long)row * K + lane] : 0.f;
+        if (QR) {
+            float t = qr_target_row(mrow, p, r[row], d[row], gamma_n, K,
+                                    lane);
+            float th = (lane < K) ? q[(long)row * K + lane] : 0.f;
+            if (lane < K) m_out[(long)row * K + lane] = t;
+            float scale = (is_weighting && w) ? w[row] : 1.f;
+            QrRow g = qr_grad_row(mrow, th, scale, B, K, kappa, per_eps,
+                                  lane);
+            if (lane < K) dlogits[(long)row * K + lane] = g.dz;
+            if (lane == 0) {
+                pri[row] = g.pri;
+                ce_acc += scale * g.loss / (float)B;
+            }
+            __builtin_amdgcn_wave_barrier();
+            continue;
+        }
         c51_project_row(mrow, p, r[row], d[row], v_min, v_max, gamma_n, K,
                         lane);
         float mv = (lane < K) ? mrow[lane] : 0.f;
@@ -127,6 +145,8 @@ __global__ void k_project_ce(const float* __restrict__ p_t,
 }
 
 // ---- policy gradient through the softmax head (K6 seed) ---------------------
+// QR: the quantile head's constant gradient and mean (qr_policy_row).
+template <bool QR>
 __global__ void k_policy_grad(const float* __restrict__ q,
                               float* __restrict__ dlogits,
                               Counters* cnt,
@@ -142,7 +162,8 @@ __global__ void k_policy_grad(const float* __restrict__ q,
          row += gridDim.x * wpb) {
         float qv = (lane < K) ? q[(long)row * K + lane] : 0.f;
         float e;
-        float dz = policy_grad_row(qv, z, B, e);
+        float dz = QR ? qr_policy_row(qv, B, K, lane, e)
+                      : policy_grad_row(qv, z, B, e);
         if (lane < K) dlogits[(long)row * K + lane] = dz;
         if (lane == 0) loss_acc += -e / (float)B;
     }

@@ -202,12 +202,13 @@ __device__ inline void t_bar(unsigned long long* tc,
 // kernel segfaults ROCm 7.2's clang in ADCE; the call overhead is noise
 // next to the ~1 us phase time.)
 // TWIN: each instantiation of k_step_persistent calls its own copy of the two
-// out-of-line helpers (p_fwd, p_dw2), the code being the same.  An
+// out-of-line helpers (p_fwd, p_dw2), the code being the same (TWIN numbers
+// the instantiation: CLIP + 2 * QR).  An
 // out-of-line function shared by two kernels changes the register allocation
 // of both (measured: the default kernel went from 598 to 658 spilled SGPRs
 // and from 84 to 216 B of scratch); with a copy each, the default kernel
 // compiles to exactly what it was before the clip-on one existed.
-template <bool TWIN>
+template <int TWIN>
 __device__ __noinline__ void p_fwd(float* lds, const float* x1, const float* x2,
                              const float* wt, const float* bias, float* y,
                              int B, int in1, int in2, int out, int act_kind,
@@ -457,7 +458,7 @@ __device__ inline void p_bwd_dx(float* lds, const float* dz, const float* wt,
 // each thread owns a 4x4 output patch (ig = tid>>4 picks 4 i's, og = tid&15
 // picks 4 o's) — 8 LDS reads + 16 FMAs per batch row.  Bias rows fold in on
 // the i0==0 tiles.  Accumulation over b is ascending.
-template <bool TWIN>                  // see p_fwd
+template <int TWIN>                   // see p_fwd
 __device__ __noinline__ void p_dw2(float* lds, const float* dz,
                                    const float* x1, const float* x2,
                                    float* dwt, float* dbias,
@@ -635,6 +636,10 @@ __device__ inline void p_sample(const StepArgs& g, int wg0,
 // distribution keeps it in LDS and computes the CE gradient/priority
 // immediately (saves a barrier and the m_proj global round-trip; q comes
 // from PH4).  m_proj is still written out for introspection/parity tests.
+// QR (the quantile head): p_t holds theta', the same wave writes the target
+// samples T to its LDS row and to m_proj and takes the quantile-Huber
+// gradient, row loss and priority from them; same loads and stores otherwise.
+template <bool QR>
 __device__ inline void p_project_ce(const StepArgs& g, float* lds,
                                     int row_base = -1) {
     int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -642,6 +647,25 @@ __device__ inline void p_project_ce(const StepArgs& g, float* lds,
     if (row >= g.B) return;
     int K = g.K;
     float* mrow = lds + wid * 64;
+    if (QR) {
+        float tp = (lane < K) ? ld_wt(&g.p_t[(long)row * K + lane]) : 0.f;
+        float t = qr_target_row(mrow, tp, g.br[row], g.bd[row], g.gamma_n, K,
+                                lane);
+        float th = 0.f;
+        if (lane < K) {
+            g.m_proj[(long)row * K + lane] = t;
+            th = g.q[(long)row * K + lane];
+        }
+        float scale = (g.is_weighting && g.bw) ? g.bw[row] : 1.f;
+        QrRow r = qr_grad_row(mrow, th, scale, g.B, K, g.kappa, g.per_eps,
+                              lane);
+        if (lane < K) g.dlog[(long)row * K + lane] = r.dz;
+        if (lane == 0) {
+            g.pri[row] = r.pri;
+            atomicAdd(&g.cnt->loss_critic, scale * r.loss / (float)g.B);
+        }
+        return;
+    }
     // p_t: this workgroup's own st_wt store of a moment ago (K <= 64 is one
     // column tile, member 0's); ld_wt so that no older L1 line can serve it.
     // q, br, bd, bw and the stores below cross a p_bar: plain.
@@ -693,6 +717,7 @@ __device__ inline void p_bwd_dx_narrow(const StepArgs& g, const float* dz,
     }
 }
 
+template <bool QR>
 __device__ inline void p_policy_grad(const StepArgs& g,
                                      int row_base = -1) {
     int row = (row_base < 0 ? (int)blockIdx.x * 4 : row_base)
@@ -706,8 +731,9 @@ __device__ inline void p_policy_grad(const StepArgs& g,
     // same, so that no older L1 line can serve them.
     float qv = (lane < K) ? ld_wt(&g.pq[(long)row * K + lane]) : 0.f;
     float e;
-    float dz = policy_grad_row(qv, c51_atom(g.v_min, g.v_max, K, lane), g.B,
-                               e);
+    float dz = QR ? qr_policy_row(qv, g.B, K, lane, e)
+                  : policy_grad_row(qv, c51_atom(g.v_min, g.v_max, K, lane),
+                                    g.B, e);
     if (lane < K) st_wt(&g.pd3[(long)row * K + lane], dz);
     if (lane == 0) atomicAdd(&g.cnt->loss_actor, -e / (float)g.B);
 }
@@ -728,10 +754,17 @@ __device__ inline void p_per_update(const StepArgs& g, int owner_wg) {
 // complete gradient slab and ONE more grid barrier between the dW phase and
 // Adam; every one of the PNWG workgroups takes that barrier, under the
 // template parameter alone (grid-uniform by construction, never data).
-// k_step_persistent<false> is the kernel without any of it.
-template <bool CLIP>
+// k_step_persistent<false, false> is the kernel without any of it.
+// QR (DIST_QUANTILE) swaps the three critic-family heads (critic,
+// critic_target, the policy chain's critic) from softmax to identity and the
+// projection/CE and policy-gradient rows for their quantile forms; phases,
+// barriers and hand-offs are the same.  A template parameter like CLIP, so
+// the categorical kernels carry no branch on it.
+template <bool CLIP, bool QR>
 __global__ void __launch_bounds__(256, 1)
 k_step_persistent(StepArgs g, int nsteps) {
+    constexpr int TW = (CLIP ? 1 : 0) + (QR ? 2 : 0);   // p_fwd / p_dw2 copy
+    constexpr int HEAD = QR ? ACT_NONE : ACT_SOFTMAX;   // critic-family head
     __shared__ float lds[PLDS_FLOATS];
     unsigned long long tgt = g.gbar[160];   // cross-launch round base
     unsigned long long* ctr = g.gbar;
@@ -787,50 +820,50 @@ k_step_persistent(StepArgs g, int nsteps) {
             PTIME(g, s, 1);
             // PH1: four independent L1s (16 wgs each)
             if (wg < PW4)
-                p_fwd<CLIP>(lds, g.bs2, nullptr, at.w1, at.b1, g.at_h1, B, O, 0,
+                p_fwd<TW>(lds, g.bs2, nullptr, at.w1, at.b1, g.at_h1, B, O, 0,
                       H, ACT_RELU, wg, PW4);
             else if (wg < 2 * PW4)
-                p_fwd<CLIP>(lds, g.bs2, nullptr, ct.w1, ct.b1, g.ct_h1, B, O, 0,
+                p_fwd<TW>(lds, g.bs2, nullptr, ct.w1, ct.b1, g.ct_h1, B, O, 0,
                       H, ACT_RELU, wg - PW4, PW4);
             else if (wg < 3 * PW4)
-                p_fwd<CLIP>(lds, bs_cur, nullptr, c.w1, c.b1, g.c_h1, B, O, 0, H,
+                p_fwd<TW>(lds, bs_cur, nullptr, c.w1, c.b1, g.c_h1, B, O, 0, H,
                       ACT_RELU, wg - 2 * PW4, PW4);
             else
-                p_fwd<CLIP>(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
+                p_fwd<TW>(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
                       ACT_RELU, wg - 3 * PW4, PW4);
             p_bar(ctr, tgt); PTIME(g, s, 2);
             // PH2: actor_t.L2 | critic.L2(cat h1, a) | actor.L2
             if (wg < PW3A)
-                p_fwd<CLIP>(lds, g.at_h1, nullptr, at.w2, at.b2, g.at_h2, B, H, 0,
+                p_fwd<TW>(lds, g.at_h1, nullptr, at.w2, at.b2, g.at_h2, B, H, 0,
                       H, ACT_NONE, wg, PW3A);
             else if (wg < 2 * PW3A)
-                p_fwd<CLIP>(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A, H,
+                p_fwd<TW>(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A, H,
                       ACT_RELU, wg - PW3A, PW3A);
             else
-                p_fwd<CLIP>(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
+                p_fwd<TW>(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
                       H, ACT_NONE, wg - 2 * PW3A, PW3B);
             p_bar(ctr, tgt); PTIME(g, s, 3);
             // PH3: L3s
             if (wg < PW3A)
-                p_fwd<CLIP>(lds, g.at_h2, nullptr, at.w3, at.b3, g.at_h3, B, H, 0,
+                p_fwd<TW>(lds, g.at_h2, nullptr, at.w3, at.b3, g.at_h3, B, H, 0,
                       H, ACT_RELU, wg, PW3A);
             else if (wg < 2 * PW3A)
-                p_fwd<CLIP>(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H, 0, H,
+                p_fwd<TW>(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H, 0, H,
                       ACT_RELU, wg - PW3A, PW3A);
             else
-                p_fwd<CLIP>(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
+                p_fwd<TW>(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
                       H, ACT_RELU, wg - 2 * PW3A, PW3B);
             p_bar(ctr, tgt); PTIME(g, s, 4);
             // PH4: heads — actor_t tanh -> a2 | critic softmax -> q |
             //      actor tanh -> a_out
             if (wg < PW3A)
-                p_fwd<CLIP>(lds, g.at_h3, nullptr, at.w4, at.b4, g.a2, B, H, 0, A,
+                p_fwd<TW>(lds, g.at_h3, nullptr, at.w4, at.b4, g.a2, B, H, 0, A,
                       ACT_TANH, wg, PW3A);
             else if (wg < 2 * PW3A)
-                p_fwd<CLIP>(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0, K,
-                      ACT_SOFTMAX, wg - PW3A, PW3A);
+                p_fwd<TW>(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0, K,
+                      HEAD, wg - PW3A, PW3A);
             else
-                p_fwd<CLIP>(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
+                p_fwd<TW>(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
                       A, ACT_TANH, wg - 2 * PW3A, PW3B);
             // per-step loss accumulators zeroed here (grid barrier below
             // orders this before the quad-chained proj-CE / pgrad adds);
@@ -861,16 +894,16 @@ k_step_persistent(StepArgs g, int nsteps) {
             int q = wg >> 2, m = wg & 3;
             unsigned long long* qc = ctr + 192 + (q << 4);
             if (pipe && wg >= QW && wg < QW + 32) {
-                p_fwd<CLIP>(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
+                p_fwd<TW>(lds, bs_cur, nullptr, a.w1, a.b1, g.pa_h1, B, O, 0, H,
                       ACT_RELU, wg - QW, 32);
                 t_bar(ctr + 1280, trnd, 32);
-                p_fwd<CLIP>(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
+                p_fwd<TW>(lds, g.pa_h1, nullptr, a.w2, a.b2, g.pa_h2, B, H, 0,
                       H, ACT_NONE, wg - QW, 32);
                 t_bar(ctr + 1280, trnd, 32);
-                p_fwd<CLIP>(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
+                p_fwd<TW>(lds, g.pa_h2, nullptr, a.w3, a.b3, g.pa_h3, B, H, 0,
                       H, ACT_RELU, wg - QW, 32);
                 t_bar(ctr + 1280, trnd, 32);
-                p_fwd<CLIP>(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
+                p_fwd<TW>(lds, g.pa_h3, nullptr, a.w4, a.b4, g.a_out, B, H, 0,
                       A, ACT_TANH, wg - QW, 32);
                 PTIMEW(g, s, 53, QW);        // actor crew's end
             }
@@ -878,29 +911,29 @@ k_step_persistent(StepArgs g, int nsteps) {
                 long r0 = (long)rg * 4;
                 int nb = min(4, B - (int)r0);
                 if (pipe) {
-                    p_fwd<CLIP>(lds, g.bs2 + r0 * O, nullptr, at.w1, at.b1,
+                    p_fwd<TW>(lds, g.bs2 + r0 * O, nullptr, at.w1, at.b1,
                           g.at_h1 + r0 * H, nb, O, 0, H, ACT_RELU, m, 4);
                     q_bar(qc, qrnd);
-                    p_fwd<CLIP>(lds, g.at_h1 + r0 * H, nullptr, at.w2, at.b2,
+                    p_fwd<TW>(lds, g.at_h1 + r0 * H, nullptr, at.w2, at.b2,
                           g.at_h2 + r0 * H, nb, H, 0, H, ACT_NONE, m, 4);
                     q_bar(qc, qrnd);
-                    p_fwd<CLIP>(lds, g.at_h2 + r0 * H, nullptr, at.w3, at.b3,
+                    p_fwd<TW>(lds, g.at_h2 + r0 * H, nullptr, at.w3, at.b3,
                           g.at_h3 + r0 * H, nb, H, 0, H, ACT_RELU, m, 4);
                     q_bar(qc, qrnd);
-                    p_fwd<CLIP>(lds, g.at_h3 + r0 * H, nullptr, at.w4, at.b4,
+                    p_fwd<TW>(lds, g.at_h3 + r0 * H, nullptr, at.w4, at.b4,
                           g.a2 + r0 * A, nb, H, 0, A, ACT_TANH, m, 4);
                     q_bar(qc, qrnd); PTIME(g, s, 54);
                 }
-                p_fwd<CLIP>(lds, g.ct_h1 + r0 * H, g.a2 + r0 * A, ct.w2, ct.b2,
+                p_fwd<TW>(lds, g.ct_h1 + r0 * H, g.a2 + r0 * A, ct.w2, ct.b2,
                       g.ct_h2 + r0 * H, nb, H, A, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd);
-                p_fwd<CLIP>(lds, g.ct_h2 + r0 * H, nullptr, ct.w3, ct.b3,
+                p_fwd<TW>(lds, g.ct_h2 + r0 * H, nullptr, ct.w3, ct.b3,
                       g.ct_h3 + r0 * H, nb, H, 0, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd);
-                p_fwd<CLIP>(lds, g.ct_h3 + r0 * H, nullptr, ct.w4, ct.b4,
-                      g.p_t + r0 * K, nb, H, 0, K, ACT_SOFTMAX, m, 4);
+                p_fwd<TW>(lds, g.ct_h3 + r0 * H, nullptr, ct.w4, ct.b4,
+                      g.p_t + r0 * K, nb, H, 0, K, HEAD, m, 4);
                 if (m == 0)
-                    p_project_ce(g, lds, (int)r0);
+                    p_project_ce<QR>(g, lds, (int)r0);
                 PTIME(g, s, 55);
                 // no trailing q_bar: row groups are independent and the
                 // closing grid barrier publishes everything
@@ -936,18 +969,18 @@ k_step_persistent(StepArgs g, int nsteps) {
         PTIME(g, s, 10); PTIME(g, s, 11); PTIME(g, s, 12);
         // PH13: critic dW, 4 jobs split by tile count (l1 is the biggest)
         if (wg < PNWG / 16)
-            p_dw2<CLIP>(lds, g.d1, bs_cur, nullptr, g.g_critic + g.cl[0].w_off,
+            p_dw2<TW>(lds, g.d1, bs_cur, nullptr, g.g_critic + g.cl[0].w_off,
                  g.g_critic + g.cl[0].b_off, B, O, 0, H, wg, PNWG / 16);
         else if (wg < PNWG / 2)
-            p_dw2<CLIP>(lds, g.d2, g.c_h1, g.ba, g.g_critic + g.cl[1].w_off,
+            p_dw2<TW>(lds, g.d2, g.c_h1, g.ba, g.g_critic + g.cl[1].w_off,
                  g.g_critic + g.cl[1].b_off, B, H, A, H, wg - PNWG / 16,
                  PNWG / 2 - PNWG / 16);
         else if (wg < PNWG * 7 / 8)
-            p_dw2<CLIP>(lds, g.d3, g.c_h2, nullptr, g.g_critic + g.cl[2].w_off,
+            p_dw2<TW>(lds, g.d3, g.c_h2, nullptr, g.g_critic + g.cl[2].w_off,
                  g.g_critic + g.cl[2].b_off, B, H, 0, H, wg - PNWG / 2,
                  PNWG * 7 / 8 - PNWG / 2);
         else
-            p_dw2<CLIP>(lds, g.dlog, g.c_h3, nullptr, g.g_critic + g.cl[3].w_off,
+            p_dw2<TW>(lds, g.dlog, g.c_h3, nullptr, g.g_critic + g.cl[3].w_off,
                  g.g_critic + g.cl[3].b_off, B, H, 0, K, wg - PNWG * 7 / 8,
                  PNWG - PNWG * 7 / 8);
         p_bar(ctr, tgt); PTIME(g, s, 13);
@@ -986,9 +1019,9 @@ k_step_persistent(StepArgs g, int nsteps) {
                 if (s + 1 < nsteps) {
                     p_sample(g, QW, ep0 + s + 1, bt0 + s + 1, bs_nxt);
                     t_bar(ctr + 1280, trnd, 32);
-                    p_fwd<CLIP>(lds, g.bs2, nullptr, ct.w1, ct.b1, g.ct_h1, B,
+                    p_fwd<TW>(lds, g.bs2, nullptr, ct.w1, ct.b1, g.ct_h1, B,
                           O, 0, H, ACT_RELU, wg - QW, 32);
-                    p_fwd<CLIP>(lds, bs_nxt, nullptr, c.w1, c.b1, g.c_h1, B, O,
+                    p_fwd<TW>(lds, bs_nxt, nullptr, c.w1, c.b1, g.c_h1, B, O,
                           0, H, ACT_RELU, wg - QW, 32);
                     // ... and the rest of the NEXT step's critic forward:
                     // the critic's weights have been final since PH14,
@@ -996,14 +1029,14 @@ k_step_persistent(StepArgs g, int nsteps) {
                     // this step's last readers of c_h* and q (PH13, the
                     // CE row) are long past
                     t_bar(ctr + 1280, trnd, 32);
-                    p_fwd<CLIP>(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A,
+                    p_fwd<TW>(lds, g.c_h1, g.ba, c.w2, c.b2, g.c_h2, B, H, A,
                           H, ACT_RELU, wg - QW, 32);
                     t_bar(ctr + 1280, trnd, 32);
-                    p_fwd<CLIP>(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H,
+                    p_fwd<TW>(lds, g.c_h2, nullptr, c.w3, c.b3, g.c_h3, B, H,
                           0, H, ACT_RELU, wg - QW, 32);
                     t_bar(ctr + 1280, trnd, 32);
-                    p_fwd<CLIP>(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0,
-                          K, ACT_SOFTMAX, wg - QW, 32);
+                    p_fwd<TW>(lds, g.c_h3, nullptr, c.w4, c.b4, g.q, B, H, 0,
+                          K, HEAD, wg - QW, 32);
                 }
                 PTIMEW(g, s, 52, QW);        // tail crew's end
             }
@@ -1011,19 +1044,19 @@ k_step_persistent(StepArgs g, int nsteps) {
                 long r0 = (long)rg * 4;
                 int nb = min(4, B - (int)r0);
                 PTIME(g, s, 40);
-                p_fwd<CLIP>(lds, bs_cur + r0 * O, nullptr, c.w1, c.b1,
+                p_fwd<TW>(lds, bs_cur + r0 * O, nullptr, c.w1, c.b1,
                       g.pc_h1 + r0 * H, nb, O, 0, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd); PTIME(g, s, 41);
-                p_fwd<CLIP>(lds, g.pc_h1 + r0 * H, g.a_out + r0 * A, c.w2, c.b2,
+                p_fwd<TW>(lds, g.pc_h1 + r0 * H, g.a_out + r0 * A, c.w2, c.b2,
                       g.pc_h2 + r0 * H, nb, H, A, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd); PTIME(g, s, 42);
-                p_fwd<CLIP>(lds, g.pc_h2 + r0 * H, nullptr, c.w3, c.b3,
+                p_fwd<TW>(lds, g.pc_h2 + r0 * H, nullptr, c.w3, c.b3,
                       g.pc_h3 + r0 * H, nb, H, 0, H, ACT_RELU, m, 4);
                 q_bar(qc, qrnd); PTIME(g, s, 43);
-                p_fwd<CLIP>(lds, g.pc_h3 + r0 * H, nullptr, c.w4, c.b4,
-                      g.pq + r0 * K, nb, H, 0, K, ACT_SOFTMAX, m, 4);
+                p_fwd<TW>(lds, g.pc_h3 + r0 * H, nullptr, c.w4, c.b4,
+                      g.pq + r0 * K, nb, H, 0, K, HEAD, m, 4);
                 if (m == 0)
-                    p_policy_grad(g, (int)r0);
+                    p_policy_grad<QR>(g, (int)r0);
                 q_bar(qc, qrnd); PTIME(g, s, 44);
                 p_bwd_dx(lds, g.pd3 + r0 * K, c.w4, 0, H, K, nb,
                          g.pc_h3 + r0 * H, ACT_RELU, g.pd2 + r0 * H, m, 4);
@@ -1057,18 +1090,18 @@ k_step_persistent(StepArgs g, int nsteps) {
         // phase; the counter tick moves to the final phase so both Adams
         // still read this step's t)
         if (wg < PNWG / 16)
-            p_dw2<CLIP>(lds, g.az1, bs_cur, nullptr, g.g_actor + g.al[0].w_off,
+            p_dw2<TW>(lds, g.az1, bs_cur, nullptr, g.g_actor + g.al[0].w_off,
                  g.g_actor + g.al[0].b_off, B, O, 0, H, wg, PNWG / 16);
         else if (wg < PNWG * 15 / 32)
-            p_dw2<CLIP>(lds, g.az2, g.pa_h1, nullptr, g.g_actor + g.al[1].w_off,
+            p_dw2<TW>(lds, g.az2, g.pa_h1, nullptr, g.g_actor + g.al[1].w_off,
                  g.g_actor + g.al[1].b_off, B, H, 0, H, wg - PNWG / 16,
                  PNWG * 15 / 32 - PNWG / 16);
         else if (wg < PNWG * 7 / 8)
-            p_dw2<CLIP>(lds, g.az3, g.pa_h2, nullptr, g.g_actor + g.al[2].w_off,
+            p_dw2<TW>(lds, g.az3, g.pa_h2, nullptr, g.g_actor + g.al[2].w_off,
                  g.g_actor + g.al[2].b_off, B, H, 0, H, wg - PNWG * 15 / 32,
                  PNWG * 7 / 8 - PNWG * 15 / 32);
         else if (wg < PNWG - 2)
-            p_dw2<CLIP>(lds, g.adz, g.pa_h3, nullptr, g.g_actor + g.al[3].w_off,
+            p_dw2<TW>(lds, g.adz, g.pa_h3, nullptr, g.g_actor + g.al[3].w_off,
                  g.g_actor + g.al[3].b_off, B, H, 0, A, wg - PNWG * 7 / 8,
                  PNWG - 2 - PNWG * 7 / 8);
         else if (!otail && wg == PNWG - 1)

@@ -86,6 +86,17 @@ __device__ inline void rb_fwd_softmax(const float* xb, float* qrow,
     }
 }
 
+// The critic-family head (out <= 64) into qrow and the global row grow:
+// softmax probabilities, or with QR the raw outputs (the quantile values).
+template <bool QR>
+__device__ inline void rb_fwd_head(const float* xb, float* qrow,
+                                   const float* wt, const float* bias,
+                                   int in_total, int out, float* grow,
+                                   int lane) {
+    if (QR) rb_fwd(xb, qrow, wt, bias, in_total, out, ACT_NONE, grow, lane);
+    else rb_fwd_softmax(xb, qrow, wt, bias, in_total, out, grow, lane);
+}
+
 // dx[i] = (sum_o dz[o] * Wt[i][o]) * act'(hprev[i]), lane-parallel over i.
 __device__ inline void rb_bwd_dx(const float* dzb, const float* wt,
                                  int in_lo, int in_hi, int in_total, int out,
@@ -108,7 +119,10 @@ __device__ inline void rb_bwd_dx(const float* dzb, const float* wt,
 }
 
 // K2: target forwards + projection + critic forward + CE grad + priorities
-// + backward-dX chain.  One wave per row, no barriers.
+// + backward-dX chain.  One wave per row, no barriers.  QR: the quantile
+// head (identity heads, target samples for the projection, quantile-Huber
+// for the CE row); the categorical instantiation carries no branch on it.
+template <bool QR>
 __global__ void __launch_bounds__(256)
 k_critic_rowblock(StepArgs g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -135,12 +149,16 @@ k_critic_rowblock(StepArgs g) {
     for (int k = lane; k < A; k += 64) L.yb[H + k] = L.aa[k];
     rb_fwd(L.yb, L.xb, ct.w2, ct.b2, H + A, H, ACT_RELU, nullptr, lane);
     rb_fwd(L.xb, L.yb, ct.w3, ct.b3, H, H, ACT_RELU, nullptr, lane);
-    rb_fwd_softmax(L.yb, L.r0, ct.w4, ct.b4, H, K,
-                   g.p_t + (long)b * K, lane);          // r0 = p_t row
+    rb_fwd_head<QR>(L.yb, L.r0, ct.w4, ct.b4, H, K,
+                    g.p_t + (long)b * K, lane);         // r0 = p_t row
 
-    // ---- C51 projection of r0 -> r1 (m row) ----
-    c51_project_row(L.r1, (lane < K) ? L.r0[lane] : 0.f, g.br[b], g.bd[b],
-                    g.v_min, g.v_max, g.gamma_n, K, lane);
+    // ---- C51 projection of r0 -> r1 (m row); QR: target samples T ----
+    if (QR)
+        qr_target_row(L.r1, (lane < K) ? L.r0[lane] : 0.f, g.br[b], g.bd[b],
+                      g.gamma_n, K, lane);
+    else
+        c51_project_row(L.r1, (lane < K) ? L.r0[lane] : 0.f, g.br[b],
+                        g.bd[b], g.v_min, g.v_max, g.gamma_n, K, lane);
     if (lane < K) g.m_proj[(long)b * K + lane] = L.r1[lane];
 
     // ---- critic(s, a) -> q (saving h1..h3) ----
@@ -153,10 +171,23 @@ k_critic_rowblock(StepArgs g) {
            g.c_h2 + (long)b * H, lane);
     rb_fwd(L.h2, L.h3, c.w3, c.b3, H, H, ACT_RELU,
            g.c_h3 + (long)b * H, lane);
-    rb_fwd_softmax(L.h3, L.r0, c.w4, c.b4, H, K, g.q + (long)b * K, lane);
+    rb_fwd_head<QR>(L.h3, L.r0, c.w4, c.b4, H, K, g.q + (long)b * K, lane);
 
     // ---- CE grad + priority (r0 = q, r1 = m) ----
-    {
+    if (QR) {
+        float th = (lane < K) ? L.r0[lane] : 0.f;
+        float scale = (g.is_weighting && g.bw) ? g.bw[b] : 1.f;
+        QrRow r = qr_grad_row(L.r1, th, scale, g.B, K, g.kappa, g.per_eps,
+                              lane);
+        if (lane < K) {
+            L.r2[lane] = r.dz;
+            g.dlog[(long)b * K + lane] = r.dz;
+        }
+        if (lane == 0) {
+            g.pri[b] = r.pri;
+            atomicAdd(&g.cnt->loss_critic, scale * r.loss / (float)g.B);
+        }
+    } else {
         float qv = (lane < K) ? L.r0[lane] : 0.f;
         float mv = (lane < K) ? L.r1[lane] : 0.f;
         float scale = (g.is_weighting && g.bw) ? g.bw[b] : 1.f;
@@ -184,7 +215,8 @@ k_critic_rowblock(StepArgs g) {
 }
 
 // K5: actor forward + critic(s, actor(s)) + policy grad + dX chain down to
-// the actor's per-layer dz's.  One wave per row.
+// the actor's per-layer dz's.  One wave per row.  QR as in k_critic_rowblock.
+template <bool QR>
 __global__ void __launch_bounds__(256)
 k_policy_rowblock(StepArgs g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -217,15 +249,21 @@ k_policy_rowblock(StepArgs g) {
     rb_fwd(L.xb, L.yb, c.w3, c.b3, H, H, ACT_RELU,
            g.pc_h3 + (long)b * H, lane);
     // yb holds pc_h3; xb holds pc_h2 — careful reuse below.
-    rb_fwd_softmax(L.yb, L.r0, c.w4, c.b4, H, K, g.pq + (long)b * K, lane);
+    rb_fwd_head<QR>(L.yb, L.r0, c.w4, c.b4, H, K, g.pq + (long)b * K, lane);
 
     // ---- policy head gradient: pd4 = -q (z - E[z]) / B ----
     {
         float qv = (lane < K) ? L.r0[lane] : 0.f;
         float e;
-        float dz = policy_grad_row(qv, c51_atom(g.v_min, g.v_max, K, lane),
-                                   g.B, e);
+        float dz = QR ? qr_policy_row(qv, g.B, K, lane, e)
+                      : policy_grad_row(qv,
+                                        c51_atom(g.v_min, g.v_max, K, lane),
+                                        g.B, e);
         if (lane < K) L.r2[lane] = dz;
+        // the quantile form also publishes the head gradient in pd3, as the
+        // persistent and wide paths do (the categorical row-block kernel
+        // keeps it in LDS only, and stays as it was)
+        if (QR && lane < K) g.pd3[(long)b * K + lane] = dz;
         if (lane == 0) atomicAdd(&g.cnt->loss_actor, -e / (float)g.B);
     }
 

@@ -1,7 +1,8 @@
 // Row and probe formulas of the train step, one device implementation each:
 // the wave-wide softmax, the C51 projection scatter, the CE and policy-head
-// gradients and the row priority, the PER descent / IS weight, the uniform
-// draw, the sample+gather both share, the leaf write and
+// gradients and the row priority, their quantile-regression counterparts
+// (target samples, quantile-Huber gradient, policy row), the PER descent / IS
+// weight, the uniform draw, the sample+gather both share, the leaf write and
 // level-synchronised path repair of the sum/min trees, the schedule-counter
 // tick and Adam's bias-correction terms.  Used by all three paths
 // (persistent, row-block, wide) and by the replay kernels, which is what keeps
@@ -108,6 +109,85 @@ __device__ __forceinline__ float policy_grad_row(float qv, float z, int B,
     e = qv * z;
     for (int s = 32; s > 0; s >>= 1) e += __shfl_xor(e, s, 64);
     return -qv * (z - e) / (float)B;
+}
+
+// ---- quantile regression (DIST_QUANTILE) -----------------------------------
+// Lane i is quantile i, tau_i = (2i + 1) / (2K); the heads are the raw fc3
+// outputs.  The weight |tau_i - 1{u < 0}| of a pair is tau_i for u >= 0 and
+// 1 - tau_i below; both are formed as one integer ratio each, so each carries
+// one rounding (1 - tau_i computed from a rounded tau_i would carry tau_i's
+// absolute error, K times larger relative to 1 / 2K).  Every product and sum
+// below is an explicit fmaf / __f*_rn, so the compiler's contraction choice
+// cannot differ between the kernels that inline these helpers.
+
+// Target samples of one row: lane's T = r + gamma_n (1 - d) theta' into the
+// wave-private LDS row trow[64] (0 on lanes >= K); returns the lane's T.
+__device__ __forceinline__ float qr_target_row(float* trow, float th_t,
+                                               float r, float d,
+                                               float gamma_n, int K,
+                                               int lane) {
+    float t = (lane < K)
+        ? __fmaf_rn(__fmul_rn(gamma_n, 1.f - d), th_t, r) : 0.f;
+    trow[lane] = t;
+    __builtin_amdgcn_wave_barrier();
+    return t;
+}
+
+// Quantile-Huber gradient of one row from trow (qr_target_row) and the lane's
+// online quantile th (0 on lanes >= K).  Lane i walks j = 0 .. K-1 ascending:
+//   u = T_j - theta_i,  w = |tau_i - 1{u < 0}|
+//   gsum += w clip(u, -kappa, kappa),  lsum += w H(u)
+// dz is the lane's head gradient scale / B * (-(gsum / kappa) / K); loss, on
+// every lane, the row loss (1/K) sum_i sum_j rho_ij before scale / B; pri, on
+// every lane, |mean_j T_j - mean_i theta_i| + per_eps.  The three wave sums
+// share one butterfly.
+struct QrRow { float dz, loss, pri; };
+
+__device__ __forceinline__ QrRow qr_grad_row(const float* trow, float th,
+                                             float scale, int B, int K,
+                                             float kappa, float per_eps,
+                                             int lane) {
+    float k2 = (float)(2 * K);
+    float w_pos = (float)(2 * lane + 1) / k2;             // tau_i
+    float w_neg = (float)(2 * K - 2 * lane - 1) / k2;     // 1 - tau_i
+    float hk = 0.5f * kappa;
+    float gsum = 0.f, lsum = 0.f;
+    for (int j = 0; j < K; ++j) {
+        float u = __fsub_rn(trow[j], th);
+        float au = fabsf(u);
+        float w = (u < 0.f) ? w_neg : w_pos;
+        float cl = fminf(fmaxf(u, -kappa), kappa);
+        float h = (au <= kappa) ? __fmul_rn(__fmul_rn(0.5f, u), u)
+                                : __fmul_rn(kappa, __fsub_rn(au, hk));
+        gsum = __fmaf_rn(w, cl, gsum);
+        lsum = __fmaf_rn(w, h, lsum);
+    }
+    bool valid = lane < K;
+    float ls = valid ? lsum / kappa : 0.f;
+    float ts = valid ? trow[lane] : 0.f;
+    float qs = valid ? th : 0.f;
+    for (int s = 32; s > 0; s >>= 1) {
+        ls += __shfl_xor(ls, s, 64);
+        ts += __shfl_xor(ts, s, 64);
+        qs += __shfl_xor(qs, s, 64);
+    }
+    float fk = (float)K;
+    QrRow r;
+    r.dz = __fmul_rn(scale / (float)B, -(gsum / kappa) / fk);
+    r.loss = ls / fk;
+    r.pri = __fadd_rn(fabsf(__fsub_rn(ts / fk, qs / fk)), per_eps);
+    return r;
+}
+
+// Policy-head gradient of one row: L = -(1/B) sum_b (1/K) sum_i theta_i, so
+// the head gradient is the constant -1 / (B K) on lanes < K.  e returns
+// mean_i theta_i, wave-reduced (the row's loss is -e / B).
+__device__ __forceinline__ float qr_policy_row(float th, int B, int K,
+                                               int lane, float& e) {
+    e = (lane < K) ? th : 0.f;
+    for (int s = 32; s > 0; s >>= 1) e += __shfl_xor(e, s, 64);
+    e = e / (float)K;
+    return -1.f / (float)(B * K);
 }
 
 // ---- PER sampling ----------------------------------------------------------

@@ -27,8 +27,15 @@ static int64_t create(int64_t obs, int64_t act, int64_t hidden, int64_t atoms,
                       double per_beta0, int64_t per_beta_iters,
                       double per_eps, int64_t seed, bool is_weighting,
                       bool prioritized, bool true_td, bool gemm_bf16,
-                      double max_grad_norm) {
+                      double max_grad_norm, const std::string& dist,
+                      double kappa) {
     EngineCfg c{};
+    if (dist == "categorical") c.dist = DIST_CATEGORICAL;
+    else if (dist == "quantile") c.dist = DIST_QUANTILE;
+    else throw std::runtime_error(
+        "unknown critic dist '" + dist +
+        "' (expected 'categorical' or 'quantile')");
+    c.kappa = (float)kappa;             // the engine refuses <= 0 and NaN
     c.obs = (int)obs; c.act = (int)act; c.hidden = (int)hidden;
     c.atoms = (int)atoms; c.batch = (int)batch;
     c.capacity = capacity;
@@ -58,6 +65,8 @@ static py::dict info(int64_t h) {
     d["true_td"] = e.cfg.true_td != 0;
     d["gemm_precision"] = e.cfg.gemm_bf16 ? "bf16" : "fp32";
     d["max_grad_norm"] = e.cfg.max_grad_norm;
+    d["dist"] = e.quantile() ? "quantile" : "categorical";
+    d["kappa"] = (double)e.cfg.kappa;
     d["persistent"] = e.step_path() == Engine::PATH_PERSISTENT;
     d["seed"] = (int64_t)e.cfg.seed;
     // episodes one collection window can hold; 0 before collect_alloc
@@ -691,7 +700,8 @@ static torch::Tensor read_buffer(int64_t h, std::string name) {
 }  // namespace d4pg
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
-    // gemm_bf16 and max_grad_norm are the trailing arguments with defaults
+    // gemm_bf16, max_grad_norm, dist and kappa are the trailing arguments
+    // with defaults
     mod.def("create", &d4pg::create,
             py::arg("obs"), py::arg("act"), py::arg("hidden"),
             py::arg("atoms"), py::arg("batch"), py::arg("capacity"),
@@ -702,7 +712,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("is_weighting"), py::arg("prioritized"),
             py::arg("true_td"),
             py::arg("gemm_bf16") = false,
-            py::arg("max_grad_norm") = 0.0);
+            py::arg("max_grad_norm") = 0.0,
+            py::arg("dist") = "categorical", py::arg("kappa") = 1.0);
     mod.def("destroy", &d4pg::destroy);
     mod.def("info", &d4pg::info);
     mod.def("load_slab", &d4pg::load_slab);

@@ -5,6 +5,7 @@ Random policy scores ~-1200..-1500; a learning agent reaches -150..-400.
 
 Usage: python scripts/gpu_train_convergence.py [cycles] [--vector_envs M]
            [--bsize B] [--gemm_precision {fp32,bf16}]
+           [--critic_dist {categorical,quantile}] [--huber_kappa KAPPA]
 
 With --vector_envs M > 0 (and a GPU) the Worker takes the closed on-GPU
 cycle: M-env device episodes collect into the learner's replay and the
@@ -20,7 +21,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from d4pg_amd.algo.d4pg import DDPG  # noqa: E402
-from d4pg_amd.config import configure_env_params, make_parser  # noqa: E402
+from d4pg_amd.config import (configure_env_params, critic_dist_info,  # noqa: E402
+                             make_parser)
 from d4pg_amd.envs import make, obs_act_dims  # noqa: E402
 from d4pg_amd.parallel.worker import Worker  # noqa: E402
 
@@ -31,6 +33,9 @@ _cli.add_argument("cycles", nargs="?", type=int, default=30)
 _cli.add_argument("--vector_envs", type=int, default=0)
 _cli.add_argument("--bsize", type=int, default=64)
 _cli.add_argument("--gemm_precision", default="fp32", choices=["fp32", "bf16"])
+_cli.add_argument("--critic_dist", default="categorical",
+                  choices=["categorical", "quantile"])
+_cli.add_argument("--huber_kappa", type=float, default=1.0)
 _opts = _cli.parse_args()
 cycles = _opts.cycles
 
@@ -41,7 +46,9 @@ args = make_parser().parse_args(
      "--episodes_per_cycle", "8", "--train_steps_per_cycle", "600",
      "--eval_trials", "3", "--seed", "0",
      "--vector_envs", str(_opts.vector_envs),
-     "--gemm_precision", _opts.gemm_precision])
+     "--gemm_precision", _opts.gemm_precision,
+     "--critic_dist", _opts.critic_dist,
+     "--huber_kappa", str(_opts.huber_kappa)])
 configure_env_params(args)
 
 env = make(args.env, seed=0)
@@ -52,8 +59,7 @@ backend = "hip" if device == "cuda" else "eager"
 agent = DDPG(obs_dim, act_dim, env=env, memory_size=args.rmsize,
              batch_size=args.bsize, gamma=args.gamma, tau=args.tau,
              prioritized_replay=True,
-             critic_dist_info={"type": "categorical", "v_min": -300.0,
-                               "v_max": 0.0, "n_atoms": 51},
+             critic_dist_info=critic_dist_info(args),
              n_steps=args.n_steps, lr_actor=1e-4, lr_critic=1e-3,
              device=device, backend=backend, seed=0,
              gemm_precision=args.gemm_precision)
