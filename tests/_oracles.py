@@ -1,6 +1,6 @@
 """Plain numpy oracles for the fused engine's PER sampling, C51 projection,
-replay ring and rollout noise streams (shared by the CPU and GPU tests; not a
-conftest).
+replay ring, rollout noise streams and fused Adam + target soft update (shared
+by the CPU and GPU tests; not a conftest).
 
 Everything here is written for clarity, not speed: python loops, float64
 mass arithmetic.  Where the engine's result depends on a float32 rounding
@@ -259,3 +259,141 @@ def edge_rows(n, K, v_min, v_max, seed=0):
             r[i], d[i] = rng.uniform(v_min + 0.05 * span,
                                      v_max - 0.05 * span), 1.0
     return r, d
+
+
+# ---------------------------------------------------------------------------
+# fused Adam + target soft update, element by element
+# ---------------------------------------------------------------------------
+
+ADAM_U = 2.0 ** -23          # the unit of tests/_wide_gemm.py
+ADAM_POW_ERR = 4 * 2.0 ** -24   # assumed absolute error of the device's b^t
+
+
+def adam_bc64(t):
+    """(bc1, bc2) = 1 - b^t in float64, b the device's float32 constants."""
+    t = float(int(t))
+    return (1.0 - float(np.float32(0.9)) ** t,
+            1.0 - float(np.float32(0.999)) ** t)
+
+
+def adam_lerp_oracle(p, g, m, v, tgt, t, lr, tau, scale=1.0, *, got):
+    """One element-wise Adam step and target soft update, float64 arithmetic
+    on float32 inputs, as k_adam_lerp / k_adam_lerp_clip / p_adam_lerp spell
+    it:
+
+        gs = scale * g                    (rounded once to float32)
+        m' = b1 m + (1 - b1) gs           v' = b2 v + (1 - b2) gs^2
+        p' = p - lr (m' / bc1) / (sqrt(v' / bc2) + eps),   bc_k = 1 - b_k^t
+        tgt' = tgt + tau (p' - tgt)
+
+    The constants are the device's: b1, b2, eps, lr, tau and scale rounded to
+    float32, 1 - b formed in float32 (both differences are exact there).
+
+    Each stage is teacher-forced on the device's own stored output of the
+    stage before (`got`: dict with the device's "m", "v", "p"), so one stage's
+    rounding never enters the next stage's comparison.  Returns
+    {name: (expected, bound)} for m, v, p, tgt, float64, elementwise.
+
+    Bounds (u = 2^-23; every float32 operation is taken to err by at most
+    2^-24 relative, or 2^-150 absolute where its result is subnormal):
+      m'   3 roundings (two products, one sum; an fma saves one):
+           3u (|b1 m| + |(1-b1) gs|) + 2^-149
+      v'   4 roundings ((1-b2) gs, that times gs, b2 v, the sum):
+           4u (b2 v + (1-b2) gs^2) + 2^-149
+      p'   u (|p_ref| + 6 |step|) + |step| (E1 + E2 / 2).  The step takes at
+           most 8 roundings (1 - b1^t, m'/bc1, 1 - b2^t and v'/bc2 under the
+           square root so halved, sqrt, + eps, lr *, the quotient), 7u/2, and
+           the final subtraction u/2 of |p'|.  E_k = ADAM_POW_ERR / bc_k is
+           the relative error bc_k inherits from the device's b_k^t; bc2
+           stands under the square root, hence E2 / 2.
+      tgt' p' - tgt, tau * that, and the sum (an fma saves one):
+           u (|tgt_ref| + 2 tau |p' - tgt|)
+    """
+    f32, f64 = np.float32, np.float64
+    b1, b2, eps = f32(0.9), f32(0.999), f32(1e-8)
+    omb1, omb2 = f64(f32(1) - b1), f64(f32(1) - b2)
+    lr, tau = f64(f32(lr)), f64(f32(tau))
+    p, g, m, v, tgt = (np.asarray(x, f32) for x in (p, g, m, v, tgt))
+    tiny = 2.0 ** -149
+    gs = (f32(scale) * g).astype(f32).astype(f64)     # one float32 rounding
+    m64, v64 = m.astype(f64), v.astype(f64)
+    m_ref = f64(b1) * m64 + omb1 * gs
+    m_bound = 3 * ADAM_U * (np.abs(f64(b1) * m64) + np.abs(omb1 * gs)) + tiny
+    v_ref = f64(b2) * v64 + omb2 * gs * gs
+    v_bound = 4 * ADAM_U * v_ref + tiny
+
+    bc1, bc2 = adam_bc64(t)
+    e1, e2 = ADAM_POW_ERR / bc1, ADAM_POW_ERR / bc2
+    dm, dv = np.asarray(got["m"], f32).astype(f64), \
+        np.asarray(got["v"], f32).astype(f64)
+    step = lr * (dm / bc1) / (np.sqrt(dv / bc2) + f64(eps))
+    p_ref = p.astype(f64) - step
+    p_bound = (ADAM_U * (np.abs(p_ref) + 6 * np.abs(step))
+               + np.abs(step) * (e1 + e2 / 2))
+
+    dp, t64 = np.asarray(got["p"], f32).astype(f64), tgt.astype(f64)
+    t_ref = t64 + tau * (dp - t64)
+    t_bound = ADAM_U * (np.abs(t_ref) + 2 * tau * np.abs(dp - t64))
+    return {"m": (m_ref, m_bound), "v": (v_ref, v_bound),
+            "p": (p_ref, p_bound), "tgt": (t_ref, t_bound)}
+
+
+# the edge classes of the Adam tests: (g, m, v, d) with tgt = p + d, except
+# where d is a callable of p.  One block of these repeats through every slab.
+def _rel(r):
+    return lambda p: (p.astype(np.float64) * r).astype(np.float32) - p
+
+
+ADAM_EDGES = [
+    # name, g, m, v, d
+    ("zero", 0.0, 0.0, 0.0, 0.5),
+    ("g+tiny", 1e-18, 0.0, 0.0, -0.25),
+    ("g-tiny", -1e-18, 0.0, 0.0, 0.25),
+    ("big+", 1e3, 1e2, 1e6, 0.0),
+    ("big-", -1e3, -1e2, 1e6, 0.0),
+    ("big+-", 1e3, -1e2, 1e6, 0.125),
+    ("cancel+", -9e-3, 1e-3, 1e-6, 0.0),
+    ("cancel-", 9e-2, -1e-2, 1e-4, 0.0),
+    ("eps+", 0.0, 1e-3, 1e-20, 0.0),
+    ("eps-", 0.0, -1e-3, 1e-20, 0.0),
+    ("tgt=p", None, None, None, 0.0),
+    ("tgt=p+1", None, None, None, 1.0),
+    ("tgt=p-1", None, None, None, -1.0),
+    ("tgt=p(1+1e-7)", None, None, None, _rel(1 + 1e-7)),
+    ("tgt=p(1-1e-7)", None, None, None, _rel(1 - 1e-7)),
+    ("tgt=1e4", None, None, None, lambda p: np.float32(1e4) - p),
+]
+ADAM_PERIOD = 61     # prime: the block lands on every thread and stride slot
+
+
+def adam_fill(n, seed, p=None, modest=False):
+    """Five float32 slabs of n elements: a seeded normal bulk (p ~ 0.1 N, g ~
+    1e-2 N, m ~ 1e-3 N, v ~ (1e-3 N)^2, tgt = p + 0.1 N: the targets are
+    decoupled from the online net) and, at every index i with i % ADAM_PERIOD
+    < len(ADAM_EDGES), edge class i % ADAM_PERIOD (None keeps the bulk value).
+    `p` overrides the bulk parameters (a real net's slab).  modest: the
+    eps-dominated classes carry m = +-1e-7, a step of about 10 * lr in place
+    of 1e5 * lr, for slabs a forward pass still has to run on after the
+    update.  Returns (dict of slabs, klass) with klass[i] the edge index or -1
+    in the bulk."""
+    f = np.float32
+    rng = np.random.default_rng(seed)
+    s = {"p": (0.1 * rng.standard_normal(n)).astype(f),
+         "g": (1e-2 * rng.standard_normal(n)).astype(f),
+         "m": (1e-3 * rng.standard_normal(n)).astype(f),
+         "v": ((1e-3 * rng.standard_normal(n)) ** 2).astype(f)}
+    if p is not None:
+        s["p"] = np.asarray(p, f).copy()
+    d = (0.1 * rng.standard_normal(n)).astype(f)
+    idx = np.arange(n) % ADAM_PERIOD
+    klass = np.where(idx < len(ADAM_EDGES), idx, -1)
+    for k, (ename, g, m, v, dd) in enumerate(ADAM_EDGES):
+        at = klass == k
+        for name, val in (("g", g), ("m", m), ("v", v)):
+            if val is not None:
+                if modest and name == "m" and ename.startswith("eps"):
+                    val = 1e-7 * np.sign(val)
+                s[name][at] = f(val)
+        d[at] = dd(s["p"][at]) if callable(dd) else f(dd)
+    s["tgt"] = (s["p"] + d).astype(f)
+    return s, klass
