@@ -52,6 +52,19 @@ def probe_mass(seed, epoch, probe, total):
     return float(u01(philox4x32_10(seed, epoch, probe)[0])) * float(total)
 
 
+def uniform_index(seed, epoch, probe, n):
+    """The uniform replay draw (tests/test_uniform_oracle.py): the first two
+    words of the PER probe's stream as a 64-bit x, slot floor(x * n / 2^64)."""
+    w = philox4x32_10(seed, epoch, probe)
+    x = (w[0] << 32) | w[1]
+    return (x * int(n)) >> 64
+
+
+def uniform_batch(seed, epoch, B, n):
+    return np.array([uniform_index(seed, epoch, i, n) for i in range(B)],
+                    np.int64)
+
+
 def build_trees(leaf_pri, tree_cap):
     """Binary-heap sum and min trees (node n has children 2n, 2n+1; leaves at
     [tree_cap, 2*tree_cap)) over `leaf_pri`, built bottom-up in float64 so
@@ -213,6 +226,31 @@ def roll_reset_state(seed, ep, env):
     th = f(f(f(2.0) * u01(v[0]) - f(1.0)) * f(3.14159265358979))
     td = f(f(2.0) * u01(v[1]) - f(1.0))
     return th, td
+
+
+def cpu_rollout(net, th0, td0, M, n_steps, horizon, gamma=0.99):
+    """Oracle: VectorPendulum + VecNStep with the SAME start state and a
+    noiseless policy; returns transitions in the device emit order
+    (tick-major, env-minor)."""
+    import torch
+    from d4pg_amd.envs.vector import VecNStep, VectorPendulum
+    env = VectorPendulum(M, seed=0, horizon=horizon)
+    env.th = np.asarray(th0, np.float64).copy()
+    env.thdot = np.asarray(td0, np.float64).copy()
+    env.t = 0
+    fold = VecNStep(M, 3, 1, n_steps, gamma)
+    obs = env._obs()
+    outs = []
+    with torch.no_grad():
+        for t in range(horizon):
+            a = net(torch.from_numpy(obs)).numpy()
+            a = np.clip(a, -1.0, 1.0).astype(np.float32)
+            obs2, r, done = env.step(a)
+            out = fold.push(obs, a, r, obs2, done)
+            if out is not None:
+                outs.append(out)
+            obs = obs2
+    return [np.concatenate([o[i] for o in outs]) for i in range(5)]
 
 
 # ---------------------------------------------------------------------------

@@ -23,18 +23,14 @@ the bound; outputs behind tanh or softmax use the 5e-5 atol of
 tests/test_gpu_wide.py.
 """
 
-import copy
-
-import numpy as np
 import torch
 
-GAMMA_N = 0.99 ** 5
-TAU, LR = 0.001, 1e-4
-V_MIN, V_MAX = -300.0, 0.0
+import _engine_kit as kit
+from _engine_kit import SLABS
+
+LR = 1e-4
 N_ROWS = 4096
 U = 2.0 ** -23
-SLABS = ["actor", "actor_target", "critic", "critic_target", "g_actor",
-         "g_critic", "m_actor", "v_actor", "m_critic", "v_critic"]
 
 # a: aligned interior tiles, odd fan-in 17, concat 134, head 51 with split-K
 # b: N edge tile 128+72, K tail of 8, B % 64 = 10, dW K = 650 (empty tail
@@ -54,39 +50,22 @@ ACTOR_BUFS = ["bs", "pa_h1", "pa_h2", "pa_h3", "a_out", "pc_h1", "pc_h2",
               "az3"]
 
 
-def _dist(c):
-    return {"type": "categorical", "v_min": V_MIN, "v_max": V_MAX,
-            "n_atoms": c["K"]}
+def _shape(c, precision="fp32", batch=None):
+    return kit.Shape(batch or c["B"], c["H"], c["O"], c["A"], c["K"],
+                     precision=precision)
 
 
 def _modules(c, seed=5):
-    from d4pg_amd.models import actor, critic
-    torch.manual_seed(seed)
-    a = actor(c["O"], c["A"], hidden=c["H"])
-    cr = critic(c["O"], c["A"], _dist(c), hidden=c["H"])
-    return a, copy.deepcopy(a), cr, copy.deepcopy(cr)
+    return kit.modules(_shape(c), seed)
 
 
 def _rows(c, seed=7):
-    rng = np.random.default_rng(seed)
-    n = N_ROWS
-    return (rng.standard_normal((n, c["O"])).astype("f"),
-            rng.uniform(-1, 1, (n, c["A"])).astype("f"),
-            rng.uniform(-30, 0, n).astype("f"),
-            rng.standard_normal((n, c["O"])).astype("f"),
-            (rng.random(n) < 0.05).astype("f"))
+    return kit.transitions(_shape(c), N_ROWS, seed)
 
 
 def _engine(c, precision="bf16", mods=None, rows=None, seed=11, batch=None):
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=c["O"], act_dim=c["A"], hidden=c["H"],
-                      n_atoms=c["K"], batch=batch or c["B"], capacity=8192,
-                      v_min=V_MIN, v_max=V_MAX, gamma_n=GAMMA_N, tau=TAU,
-                      lr_actor=LR, lr_critic=LR, seed=seed,
-                      gemm_precision=precision)
-    eng.load_from_modules(*(mods or _modules(c)))
-    eng.ingest(*[torch.from_numpy(x) for x in (rows or _rows(c))])
-    return eng
+    return kit.engine(_shape(c, precision, batch), mods or _modules(c),
+                      rows or _rows(c), capacity=8192, seed=seed)
 
 
 # ---------------------------------------------------------------------------

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
 import _oracles as orc
 from d4pg_amd.envs.vector import VectorGoalReach, VectorSynthetic
 
@@ -43,24 +44,17 @@ GOAL_SPEED, GOAL_TOL = 0.1, 0.3
 
 @functools.lru_cache(maxsize=None)
 def _nets(o, a):
-    from d4pg_amd.models import actor, critic
-    torch.manual_seed(4)
-    net = actor(o, a, hidden=H)
-    with torch.no_grad():
-        net.fc3.weight.mul_(60.0)       # spread the actions over (-1, 1)
-    torch.manual_seed(1)
-    return net, critic(o, a, DIST, hidden=H)
+    # head times 60: spread the actions over (-1, 1)
+    return kit.producer_nets(o, a, DIST, hidden=H, actor_seed=4,
+                             critic_seed=1, head_gain=60.0)
 
 
 def make_engine(o, a, batch=64, prioritized=True):
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=o, act_dim=a, hidden=H, n_atoms=K, batch=batch,
-                      capacity=CAP, v_min=-50.0, v_max=1.0,
-                      gamma_n=0.99 ** 3, tau=0.001, lr_actor=1e-3,
-                      lr_critic=1e-3, seed=0, prioritized=prioritized)
-    net, c = _nets(o, a)
-    eng.load_from_modules(net, net, c, c)
-    return eng
+    return kit.producer_engine(
+        o, a, hidden=H, n_atoms=K, capacity=CAP, batch=batch, seed=0,
+        v_min=-50.0, v_max=1.0, gamma_n=0.99 ** 3, lr=1e-3,
+        prioritized=prioritized, actor_seed=4, critic_seed=1,
+        head_gain=60.0)[0]
 
 
 def alloc(eng, kind):

@@ -24,35 +24,23 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
+
 pytestmark = pytest.mark.gpu
 
 O, A, H, K, B = 3, 1, 256, 51, 64
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def make_engine(seed=0, capacity=4096, init_params=True):
-    from d4pg_amd.models import actor, critic
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                      capacity=capacity, v_min=-300.0, v_max=0.0,
-                      gamma_n=0.99 ** 5, tau=0.001, lr_actor=1e-4,
-                      lr_critic=1e-4, seed=seed)
-    if init_params:
-        torch.manual_seed(seed)
-        a = actor(O, A, hidden=H)
-        c = critic(O, A, {"type": "categorical", "v_min": -300.0,
-                          "v_max": 0.0, "n_atoms": K}, hidden=H)
-        eng.load_from_modules(a, a, c, c)
-    return eng
+def make_engine(seed=0, capacity=4096, shape=kit.Shape(B, H, O, A, K)):
+    """Engine and nets share the seed; the targets ARE the online nets."""
+    a, _, c, _ = kit.modules(shape, seed)
+    return kit.engine(shape, (a, a, c, c), capacity=capacity, seed=seed)
 
 
 def fill(eng, seed=3, n=1024):
-    rng = np.random.default_rng(seed)
-    eng.ingest(torch.from_numpy(rng.standard_normal((n, O)).astype("f")),
-               torch.from_numpy(rng.uniform(-1, 1, (n, A)).astype("f")),
-               torch.from_numpy(rng.uniform(-30, 0, n).astype("f")),
-               torch.from_numpy(rng.standard_normal((n, O)).astype("f")),
-               torch.from_numpy(np.zeros(n, np.float32)))
+    eng.ingest(*[torch.from_numpy(x) for x in kit.transitions(
+        kit.Shape(B, H, O, A, K), n, seed, p_done=0.0)])
 
 
 def test_rccl_world1_init_and_collectives():
@@ -216,19 +204,8 @@ def test_split_step_matches_full_step_wide_mfma_path():
     """Split-step (DP insertion points) parity on the WIDE path too —
     B > 512 takes the per-layer MFMA kernels, a different code path from
     the row-block form covered above."""
-    from d4pg_amd.models import actor, critic
-    from d4pg_amd.ops import FusedEngine
-
     def mk(seed):
-        eng = FusedEngine(obs_dim=17, act_dim=6, hidden=256, n_atoms=51,
-                          batch=1024, capacity=8192, v_min=-300.0,
-                          v_max=0.0, gamma_n=0.99 ** 5, tau=0.001,
-                          lr_actor=1e-4, lr_critic=1e-4, seed=seed)
-        torch.manual_seed(seed)
-        a = actor(17, 6, hidden=256)
-        c = critic(17, 6, {"type": "categorical", "v_min": -300.0,
-                           "v_max": 0.0, "n_atoms": 51}, hidden=256)
-        eng.load_from_modules(a, a, c, c)
+        eng = make_engine(seed, 8192, kit.Shape(1024, 256, 17, 6, 51))
         eng.synth_fill(8192, seed=seed + 3)
         return eng
 

@@ -13,41 +13,29 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
+
 pytestmark = pytest.mark.gpu
 
-DIST = {"type": "categorical", "v_min": -300.0, "v_max": 0.0, "n_atoms": 51}
 O, A, H, K, B = 3, 1, 256, 51, 64
 GAMMA_N = 0.99 ** 5
 TAU = 0.001
 LR = 1e-4
 
 
+SHAPE = kit.Shape(B, H, O, A, K)
+
+
 def make_engine(seed=0, capacity=4096):
-    from d4pg_amd.ops import FusedEngine
-    return FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                       capacity=capacity, v_min=-300.0, v_max=0.0,
-                       gamma_n=GAMMA_N, tau=TAU, lr_actor=LR, lr_critic=LR,
-                       seed=seed)
+    return kit.engine(SHAPE, capacity=capacity, seed=seed)
 
 
 def make_modules(seed=0):
-    from d4pg_amd.models import actor, critic
-    torch.manual_seed(seed)
-    a = actor(O, A)
-    c = critic(O, A, DIST)
-    at = copy.deepcopy(a)
-    ct = copy.deepcopy(c)
-    return a, at, c, ct
+    return kit.modules(SHAPE, seed)
 
 
 def random_transitions(n, seed=0):
-    rng = np.random.default_rng(seed)
-    s = rng.standard_normal((n, O)).astype(np.float32)
-    a = rng.uniform(-1, 1, (n, A)).astype(np.float32)
-    r = rng.uniform(-30, 0, n).astype(np.float32)
-    s2 = rng.standard_normal((n, O)).astype(np.float32)
-    d = (rng.random(n) < 0.05).astype(np.float32)
-    return s, a, r, s2, d
+    return kit.transitions(SHAPE, n, seed)
 
 
 @pytest.fixture(scope="module")
@@ -247,11 +235,8 @@ def test_actor_forward_512_rows_at_batch_512():
     row-block there, while a forward over 512 rows already takes the MFMA
     kernels (split-K tanh head with its partials in the dW scratch)."""
     from d4pg_amd.models import actor
-    from d4pg_amd.ops import FusedEngine, pack_net
-    eng = FusedEngine(obs_dim=O, act_dim=A, hidden=64, n_atoms=K, batch=512,
-                      capacity=1024, v_min=-300.0, v_max=0.0,
-                      gamma_n=GAMMA_N, tau=TAU, lr_actor=LR, lr_critic=LR,
-                      seed=4)
+    from d4pg_amd.ops import pack_net
+    eng = kit.engine(kit.Shape(512, 64, O, A, K), capacity=1024, seed=4)
     torch.manual_seed(5)
     a = actor(O, A, hidden=64)
     eng.load_slab("actor", pack_net(a))

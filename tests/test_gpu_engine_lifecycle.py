@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
 from d4pg_amd.envs.vector import VectorSynthetic
 
 pytestmark = pytest.mark.gpu
@@ -23,24 +24,12 @@ GAMMA = 0.99
 KINDS = ["pendulum", "goal", "synth"]
 
 
-def _modules(o):
-    from d4pg_amd.models import actor, critic
-    torch.manual_seed(4)
-    a = actor(o, 1, hidden=H)
-    c = critic(o, 1, {"type": "categorical", "v_min": -10.0, "v_max": 1.0,
-                      "n_atoms": K}, hidden=H)
-    return a, c
-
-
 def _engine(o, batch):
     """One fixed initial state: seed, slabs and replay fill."""
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=o, act_dim=1, hidden=H, n_atoms=K, batch=batch,
-                      capacity=CAP, v_min=-10.0, v_max=1.0,
-                      gamma_n=GAMMA ** N, tau=0.001, lr_actor=1e-4,
-                      lr_critic=1e-4, seed=3)
-    a, c = _modules(o)
-    eng.load_from_modules(a, a, c, c)
+    eng, _ = kit.producer_engine(
+        o, 1, hidden=H, n_atoms=K, capacity=CAP, batch=batch, seed=3,
+        v_min=-10.0, v_max=1.0, gamma_n=GAMMA ** N, lr=1e-4, actor_seed=4,
+        critic_seed=None)
     eng.synth_fill(200, seed=7)
     return eng
 

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
 import _oracles as orc
 import _synth_oracles as so
 from d4pg_amd.envs.vector import (PhiloxProcNoise, VectorGoalReach,
@@ -38,26 +39,17 @@ DIST = {"type": "categorical", "v_min": -50.0, "v_max": 1.0, "n_atoms": K}
 
 @functools.lru_cache(maxsize=None)
 def _net(o, a, seed=4, gain=60.0):
-    from d4pg_amd.models import actor
-    torch.manual_seed(seed)
-    net = actor(o, a, hidden=H)
-    with torch.no_grad():
-        net.fc3.weight.mul_(gain)       # spread the actions over (-1, 1)
-    return net
+    # the gain spreads the actions over (-1, 1)
+    return kit.producer_nets(o, a, DIST, hidden=H, actor_seed=seed,
+                             critic_seed=1, head_gain=gain)[0]
 
 
 def make_engine(o, a, capacity=1024, prioritized=True, net=None):
-    from d4pg_amd.models import critic
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=o, act_dim=a, hidden=H, n_atoms=K, batch=64,
-                      capacity=capacity, v_min=-50.0, v_max=1.0,
-                      gamma_n=0.99 ** 3, tau=0.001, lr_actor=1e-3,
-                      lr_critic=1e-3, seed=0, prioritized=prioritized)
-    torch.manual_seed(1)
-    c = critic(o, a, DIST, hidden=H)
-    net = net or _net(o, a)
-    eng.load_from_modules(net, net, c, c)
-    return eng
+    return kit.producer_engine(
+        o, a, hidden=H, n_atoms=K, capacity=capacity, batch=64, seed=0,
+        v_min=-50.0, v_max=1.0, gamma_n=0.99 ** 3, lr=1e-3,
+        prioritized=prioritized, actor_seed=4, critic_seed=1, head_gain=60.0,
+        actor=net)[0]
 
 
 def _synth_vec(o, a, m, hor, proc_noise=None, sigma=0.01):

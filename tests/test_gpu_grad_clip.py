@@ -14,70 +14,39 @@ norms of its gradient slabs, "both" = 0.5 * min(Na, Nc) clips both nets and
 "one" = sqrt(Na * Nc) clips exactly the net with the larger norm.
 """
 
-import copy
 import functools
 import math
 
 import numpy as np
 import pytest
-import torch
+
+import _engine_kit as kit
 
 pytestmark = pytest.mark.gpu
 
-V_MIN, V_MAX = -300.0, 0.0
 GAMMA_N = 0.99 ** 5
 TAU, LR = 0.001, 1e-4
 CAP, N = 4096, 1024
 CHUNK = 4096                     # GN_CHUNK of ops/hip/engine_rowmath.hip
-SLABS = ["actor", "actor_target", "critic", "critic_target", "g_actor",
-         "g_critic", "m_actor", "v_actor", "m_critic", "v_critic"]
 NETS = ("actor", "critic")
-LAYERS = ["fc1", "fc2", "fc2_2", "fc3"]
 
 
-class Shape:
-    def __init__(self, B, H, O, A, K, prioritized=True, precision="fp32"):
-        self.B, self.H, self.O, self.A, self.K = B, H, O, A, K
-        self.prioritized, self.precision = prioritized, precision
-        self.dist = {"type": "categorical", "v_min": V_MIN, "v_max": V_MAX,
-                     "n_atoms": K}
-        self.path = ("persistent" if B <= 256 else
-                     "rowblock" if B <= 512 else "wide")
-
-    def __repr__(self):
-        return (f"B{self.B}-H{self.H}-O{self.O}-A{self.A}-K{self.K}"
-                + ("" if self.prioritized else "-uniform")
-                + ("" if self.precision == "fp32" else "-" + self.precision))
+class Shape(kit.Shape):
+    """The kit's shape with its inputs (seed B) and its unclipped first step
+    computed once and shared."""
 
     @functools.lru_cache(maxsize=None)
     def modules(self):
-        from d4pg_amd.models import actor, critic
-        torch.manual_seed(self.B)
-        a = actor(self.O, self.A, hidden=self.H)
-        c = critic(self.O, self.A, self.dist, hidden=self.H)
-        return a, copy.deepcopy(a), c, copy.deepcopy(c)
+        return kit.modules(self, self.B)
 
     @functools.lru_cache(maxsize=None)
     def transitions(self):
-        rng = np.random.default_rng(self.B)
-        return (rng.standard_normal((N, self.O)).astype("f"),
-                rng.uniform(-1, 1, (N, self.A)).astype("f"),
-                rng.uniform(-30, 0, N).astype("f"),
-                rng.standard_normal((N, self.O)).astype("f"),
-                (rng.random(N) < 0.05).astype("f"))
+        return kit.transitions(self, N, self.B)
 
-    def engine(self, max_grad_norm=None, seed=13):
+    def engine(self, max_grad_norm=None):
         """max_grad_norm None: an engine built without the argument."""
-        from d4pg_amd.ops import FusedEngine
-        kw = {} if max_grad_norm is None else {"max_grad_norm": max_grad_norm}
-        eng = FusedEngine(obs_dim=self.O, act_dim=self.A, hidden=self.H,
-                          n_atoms=self.K, batch=self.B, capacity=CAP,
-                          v_min=V_MIN, v_max=V_MAX, gamma_n=GAMMA_N, tau=TAU,
-                          lr_actor=LR, lr_critic=LR, seed=seed,
-                          prioritized=self.prioritized,
-                          gemm_precision=self.precision, **kw)
-        eng.load_from_modules(*self.modules())
-        eng.ingest(*[torch.from_numpy(x) for x in self.transitions()])
+        eng = kit.engine(self, self.modules(), self.transitions(),
+                         capacity=CAP, max_grad_norm=max_grad_norm)
         assert eng._persistent == (self.path == "persistent")
         return eng
 
@@ -117,10 +86,11 @@ PER_PATH = [P50, RB, WIDE]           # one shape per path
 
 
 def _slabs(eng):
-    return {n: eng.store_slab(n).numpy() for n in SLABS}
+    return kit.snapshot(eng, [], counters=[])[0]
 
 
 def _same(x, y, what):
+    assert x.keys() == y.keys()
     for k in x:
         assert np.array_equal(x[k], y[k]), f"{what}: {k} differs"
 
@@ -363,15 +333,6 @@ def test_threshold_that_never_binds_changes_nothing(shape):
 # 7. against the eager backend
 # ---------------------------------------------------------------------------
 
-def _pack(module, get):
-    parts = []
-    for n in LAYERS:
-        lin = getattr(module, n)
-        parts.append(get(lin.weight).t().contiguous().reshape(-1))
-        parts.append(get(lin.bias).reshape(-1))
-    return torch.cat(parts).detach().numpy()
-
-
 @pytest.mark.parametrize("shape", PER_PATH, ids=repr)
 def test_three_steps_match_the_eager_backend(shape):
     """DDPG(backend="eager", max_grad_norm=c) on the batches the engine drew.
@@ -396,14 +357,9 @@ def test_three_steps_match_the_eager_backend(shape):
         ag._train_step_eager(tuple(t[idx] for t in tr) + (None, None))
     st = eng.grad_stats()
     assert st["scale_actor"] < 1.0 or st["scale_critic"] < 1.0
-    want = {"actor": _pack(ag.actor, lambda p: p),
-            "actor_target": _pack(ag.actor_target, lambda p: p),
-            "critic": _pack(ag.critic, lambda p: p),
-            "critic_target": _pack(ag.critic_target, lambda p: p)}
-    for tag, net, opt in (("actor", ag.actor, ag.optimizer_actor),
-                          ("critic", ag.critic, ag.optimizer_critic)):
-        want["m_" + tag] = _pack(net, lambda p: opt.state[p]["exp_avg"])
-        want["v_" + tag] = _pack(net, lambda p: opt.state[p]["exp_avg_sq"])
+    want = kit.slabs_of(ag.actor, ag.actor_target, ag.critic,
+                        ag.critic_target, ag.optimizer_actor,
+                        ag.optimizer_critic)
     got = {n: eng.store_slab(n).numpy() for n in want}
     for n in want:
         print(f"{shape!r} {n}: max abs err {np.abs(got[n] - want[n]).max():.3g}"

@@ -14,65 +14,25 @@ never.  Two nets:
 Shapes: the smallest at which a hand-off can go wrong.
 """
 
-import copy
-
 import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
+from _engine_kit import PARAMS, Shape
+
 pytestmark = pytest.mark.gpu
 
-V_MIN, V_MAX = -300.0, 0.0
-GAMMA_N = 0.99 ** 5
-TAU, LR = 0.001, 1e-4
 CAP, N = 4096, 1024
-PARAMS = ["actor", "actor_target", "critic", "critic_target"]
-SLABS = PARAMS + ["g_actor", "g_critic", "m_actor", "v_actor", "m_critic",
-                  "v_critic"]
 # intermediates both paths write and read() exposes
 INTERMEDIATES = ["q", "a_out", "pri", "a2", "p_t", "m_proj", "dlog", "pq"]
 BATCH = ["bidx", "bs", "bs2", "ba", "br", "bd", "bw"]
-INT_COUNTERS = ["beta_t", "adam_t_actor", "adam_t_critic", "rng_epoch",
-                "size", "pos"]
 
 
-class Shape:
-    def __init__(self, B, H, O, A, K, prioritized=True):
-        self.B, self.H, self.O, self.A, self.K = B, H, O, A, K
-        self.prioritized = prioritized
-        self.dist = {"type": "categorical", "v_min": V_MIN, "v_max": V_MAX,
-                     "n_atoms": K}
-
-    def __repr__(self):
-        return (f"B{self.B}-H{self.H}-O{self.O}-A{self.A}-K{self.K}"
-                + ("" if self.prioritized else "-uniform"))
-
-    def modules(self, seed):
-        from d4pg_amd.models import actor, critic
-        torch.manual_seed(seed)
-        a = actor(self.O, self.A, hidden=self.H)
-        c = critic(self.O, self.A, self.dist, hidden=self.H)
-        return a, copy.deepcopy(a), c, copy.deepcopy(c)
-
-    def transitions(self, n, seed):
-        rng = np.random.default_rng(seed)
-        return (rng.standard_normal((n, self.O)).astype("f"),
-                rng.uniform(-1, 1, (n, self.A)).astype("f"),
-                rng.uniform(-30, 0, n).astype("f"),
-                rng.standard_normal((n, self.O)).astype("f"),
-                (rng.random(n) < 0.05).astype("f"))
-
-    def engine(self, mods, tr, seed=13):
-        from d4pg_amd.ops import FusedEngine
-        eng = FusedEngine(obs_dim=self.O, act_dim=self.A, hidden=self.H,
-                          n_atoms=self.K, batch=self.B, capacity=CAP,
-                          v_min=V_MIN, v_max=V_MAX, gamma_n=GAMMA_N, tau=TAU,
-                          lr_actor=LR, lr_critic=LR, seed=seed,
-                          prioritized=self.prioritized)
-        eng.load_from_modules(*mods)
-        eng.ingest(*[torch.from_numpy(x) for x in tr])
-        assert eng._persistent
-        return eng
+def _engine(shape, mods, tr):
+    eng = kit.engine(shape, mods, tr, capacity=CAP)
+    assert eng._persistent
+    return eng
 
 
 SHAPES = [
@@ -111,9 +71,9 @@ def test_persistent_step_matches_handoff_free_rowblock(shape):
     test_gpu_dist.py::test_split_step_matches_full_step, rtol 1e-6 / atol
     1e-7 — the two paths' Adam spellings differ in FMA rounding, nothing
     else may — except the arrays of PARENT_MAX_ABS."""
-    mods = shape.modules(seed=shape.B)
-    tr = shape.transitions(N, seed=shape.B)
-    e1, e2 = shape.engine(mods, tr), shape.engine(mods, tr)
+    mods = kit.modules(shape, seed=shape.B)
+    tr = kit.transitions(shape, N, seed=shape.B)
+    e1, e2 = _engine(shape, mods, tr), _engine(shape, mods, tr)
     e1.step(1)
     for mask in (e2.PH_CRITIC_GRADS, e2.PH_CRITIC_APPLY, e2.PH_ACTOR_GRADS,
                  e2.PH_ACTOR_APPLY):
@@ -141,12 +101,8 @@ def test_persistent_step_matches_handoff_free_rowblock(shape):
 
 
 def _state(eng):
-    st = {"slab:" + n: eng.store_slab(n).numpy() for n in SLABS}
-    st.update({n: eng.read(n).numpy()
-               for n in ["sum_tree", "min_tree", "q", "a_out", "pri"] + BATCH})
-    cnt = eng.counters()
-    st.update({"cnt:" + n: cnt[n] for n in INT_COUNTERS})
-    return st
+    return kit.snapshot(
+        eng, ["sum_tree", "min_tree", "q", "a_out", "pri"] + BATCH)[0]
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=repr)
@@ -157,9 +113,9 @@ def test_multistep_launch_under_uneven_load_is_bitwise(shape):
     must equal 12 quiet one-step launches bit for bit.  The side stream
     depends on nothing of the engine's, so the co-resident grid is still
     admitted."""
-    mods = shape.modules(seed=shape.B + 1)
-    tr = shape.transitions(N, seed=shape.B + 1)
-    x, y = shape.engine(mods, tr), shape.engine(mods, tr)
+    mods = kit.modules(shape, seed=shape.B + 1)
+    tr = kit.transitions(shape, N, seed=shape.B + 1)
+    x, y = _engine(shape, mods, tr), _engine(shape, mods, tr)
     for _ in range(12):
         y.step(1)
     ref = _state(y)

@@ -11,11 +11,10 @@ the kernel.  What runs only for s > 0 differs by batch size:
   96 < B <= 256  every step re-samples in its first phase    (B = 128)
 """
 
-import copy
-
 import numpy as np
 import pytest
-import torch
+
+import _engine_kit as kit
 
 pytestmark = pytest.mark.gpu
 
@@ -23,131 +22,38 @@ O, A, H, K = 5, 2, 128, 51
 V_MIN, V_MAX = -300.0, 0.0
 GAMMA_N = 0.99 ** 5
 TAU, LR = 0.001, 1e-4
-DIST = {"type": "categorical", "v_min": V_MIN, "v_max": V_MAX, "n_atoms": K}
 N = 512
-LAYERS = ["fc1", "fc2", "fc2_2", "fc3"]
-SLABS = ["actor", "actor_target", "critic", "critic_target", "g_actor",
-         "g_critic", "m_actor", "v_actor", "m_critic", "v_critic"]
 BUFFERS = ["sum_tree", "min_tree", "bidx", "pri", "bw", "br", "bd", "ba",
            "bs2", "m_proj", "q"]
-INT_COUNTERS = ["beta_t", "adam_t_actor", "adam_t_critic", "rng_epoch",
-                "size", "pos"]
+
+
+def _shape(B):
+    return kit.Shape(B, H, O, A, K)
 
 
 def _modules(seed=0):
-    from d4pg_amd.models import actor, critic
-    torch.manual_seed(seed)
-    a = actor(O, A, hidden=H)
-    c = critic(O, A, DIST, hidden=H)
-    return a, copy.deepcopy(a), c, copy.deepcopy(c)
+    return kit.modules(_shape(0), seed)
 
 
 def _transitions(seed=0):
-    rng = np.random.default_rng(seed)
-    return (rng.standard_normal((N, O)).astype("f"),
-            rng.uniform(-1, 1, (N, A)).astype("f"),
-            rng.uniform(-30, 0, N).astype("f"),
-            rng.standard_normal((N, O)).astype("f"),
-            (rng.random(N) < 0.05).astype("f"))
+    return kit.transitions(_shape(0), N, seed)
 
 
 def _engine(B, mods, tr, seed=13):
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                      capacity=N, v_min=V_MIN, v_max=V_MAX, gamma_n=GAMMA_N,
-                      tau=TAU, lr_actor=LR, lr_critic=LR, seed=seed)
-    eng.load_from_modules(*mods)
-    eng.ingest(*[torch.from_numpy(x) for x in tr])
-    return eng
+    return kit.engine(_shape(B), mods, tr, capacity=N, seed=seed)
 
 
 def _state(eng):
-    st = {"slab:" + n: eng.store_slab(n).numpy() for n in SLABS}
-    st.update({n: eng.read(n).numpy() for n in BUFFERS})
-    cnt = eng.counters()
-    st.update({"cnt:" + n: cnt[n] for n in INT_COUNTERS})
-    return st, cnt
+    return kit.snapshot(eng, BUFFERS)
 
 
-def _assert_same(x, y, what):
-    sx, cx = x
-    sy, cy = y
-    for k in sx:
-        assert np.array_equal(sx[k], sy[k]), f"{what}: {k} differs"
-    # the loss scalars accumulate through cross-workgroup fp32 atomics,
-    # whose order is not fixed: approximately equal only
-    for k in ("loss_critic", "loss_actor"):
-        assert cx[k] == pytest.approx(cy[k], rel=1e-5), f"{what}: {k}"
+_assert_same = kit.assert_bitwise
+_assert_bs_is_gathered = kit.assert_bs_is_gathered
 
 
-def _assert_bs_is_gathered(eng, what):
-    """read('bs') resolves the parity buffer the last step used."""
-    idx = eng.read("bidx").numpy()
-    assert np.array_equal(eng.read("bs").numpy(), eng.replay_rows()[0][idx]), \
-        f"{what}: bs is not the gathered batch"
-
-
-# ---------------------------------------------------------------------------
-# eager torch replica of one train step on a given batch
-# ---------------------------------------------------------------------------
-
-def _pack(module, get):
-    """Flatten per-parameter tensors into the engine slab layout."""
-    parts = []
-    for n in LAYERS:
-        lin = getattr(module, n)
-        parts.append(get(lin.weight).t().contiguous().reshape(-1))
-        parts.append(get(lin.bias).reshape(-1))
-    return torch.cat(parts).detach().numpy()
-
-
-class Eager:
-    def __init__(self, mods):
-        self.a, self.at, self.c, self.ct = [copy.deepcopy(m) for m in mods]
-        self.opt_c = torch.optim.Adam(self.c.parameters(), lr=LR)
-        self.opt_a = torch.optim.Adam(self.a.parameters(), lr=LR)
-
-    def step(self, s, act, r, s2, d):
-        """critic Adam, policy gradient through the UPDATED critic, actor
-        Adam, both soft updates (test_post_step_params_parity's order)."""
-        from d4pg_amd.algo.projection import categorical_projection
-        s, act, r, s2, d = [torch.from_numpy(x) for x in (s, act, r, s2, d)]
-        with torch.no_grad():
-            m = categorical_projection(self.ct(s2, self.at(s2)), r, d, V_MIN,
-                                       V_MAX, GAMMA_N)
-        q = self.c(s, act)
-        loss_c = -(m * torch.log(q + 1e-10)).sum(1).mean()
-        self.c.zero_grad()
-        loss_c.backward()
-        # (the policy loss below also backpropagates into the critic)
-        self.g_critic = _pack(self.c, lambda p: p.grad.clone())
-        self.opt_c.step()
-        z = torch.linspace(V_MIN, V_MAX, K).reshape(-1, 1)
-        pl = -(self.c(s, self.a(s)).matmul(z)).mean()
-        self.a.zero_grad()
-        pl.backward()
-        self.opt_a.step()
-        with torch.no_grad():
-            for tp, sp in zip(self.at.parameters(), self.a.parameters()):
-                tp.lerp_(sp, TAU)
-            for tp, sp in zip(self.ct.parameters(), self.c.parameters()):
-                tp.lerp_(sp, TAU)
-
-    def grads(self):
-        """Gradients of the LAST step, in the engine's slab layout."""
-        return {"g_actor": _pack(self.a, lambda p: p.grad),
-                "g_critic": self.g_critic}
-
-    def slabs(self):
-        out = {"actor": _pack(self.a, lambda p: p),
-               "actor_target": _pack(self.at, lambda p: p),
-               "critic": _pack(self.c, lambda p: p),
-               "critic_target": _pack(self.ct, lambda p: p)}
-        for tag, net, opt in (("actor", self.a, self.opt_a),
-                              ("critic", self.c, self.opt_c)):
-            out["m_" + tag] = _pack(net, lambda p: opt.state[p]["exp_avg"])
-            out["v_" + tag] = _pack(net, lambda p: opt.state[p]["exp_avg_sq"])
-        return out
+def Eager(mods):
+    return kit.Eager(mods, LR, TAU,
+                     head=kit.CategoricalHead(V_MIN, V_MAX, GAMMA_N, K))
 
 
 # ---------------------------------------------------------------------------

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
 import _oracles as orc
 
 pytestmark = pytest.mark.gpu
@@ -20,50 +21,28 @@ pytestmark = pytest.mark.gpu
 O, A, H, K = 5, 2, 128, 51
 V_MIN, V_MAX = -300.0, 0.0
 GAMMA_N = 0.99 ** 5
-DIST = {"type": "categorical", "v_min": V_MIN, "v_max": V_MAX, "n_atoms": K}
 ALPHA = float(np.float32(0.6))          # the engine holds per_alpha as float
 BETA0, BETA_ITERS = 0.4, 10
 SEED = 21
+_inject = kit.inject_replay
+
+
+def _shape(B=0):
+    return kit.Shape(B, H, O, A, K)
 
 
 def _engine(B, capacity, is_weighting=False):
-    from d4pg_amd.ops import FusedEngine
-    return FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                       capacity=capacity, v_min=V_MIN, v_max=V_MAX,
-                       gamma_n=GAMMA_N, tau=0.001, lr_actor=1e-4,
-                       lr_critic=1e-4, per_beta0=BETA0,
-                       per_beta_iters=BETA_ITERS, seed=SEED,
-                       is_weighting=is_weighting)
+    return kit.engine(_shape(B), capacity=capacity, seed=SEED,
+                      per_beta0=BETA0, per_beta_iters=BETA_ITERS,
+                      is_weighting=is_weighting)
 
 
 def _modules(seed=0):
-    from d4pg_amd.models import actor, critic
-    torch.manual_seed(seed)
-    a = actor(O, A, hidden=H)
-    c = critic(O, A, DIST, hidden=H)
-    return a, copy.deepcopy(a), c, copy.deepcopy(c)
+    return kit.modules(_shape(), seed)
 
 
 def _replay(size, seed=0):
-    rng = np.random.default_rng(seed)
-    return dict(
-        s=rng.standard_normal((size, O)).astype("f"),
-        a=rng.uniform(-1, 1, (size, A)).astype("f"),
-        r=rng.uniform(-30, 0, size).astype("f"),
-        s2=rng.standard_normal((size, O)).astype("f"),
-        d=(rng.random(size) < 0.05).astype("f"),
-        leaves=np.exp(rng.uniform(np.log(1e-3), np.log(1e3), size)))
-
-
-def _inject(eng, rp, max_priority=1.0):
-    cap = eng.info()["tree_cap"]
-    size = len(rp["r"])
-    st, mt = orc.build_trees(rp["leaves"], cap)
-    eng.ext.load_replay_state(
-        eng.h, *[torch.from_numpy(rp[k]) for k in ("s", "a", "r", "s2", "d")],
-        torch.from_numpy(st), torch.from_numpy(mt), size, size,
-        max_priority)
-    return st, mt, cap
+    return kit.per_replay(_shape(), size, seed)
 
 
 def test_fresh_engine_tree_fill():

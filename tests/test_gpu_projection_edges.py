@@ -8,12 +8,11 @@ with Tz exactly on an atom, and K in {28, 55} where float32
 every clamped atom added its mass one float past the LDS row.
 """
 
-import copy
-
 import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
 import _oracles as orc
 
 pytestmark = pytest.mark.gpu
@@ -38,18 +37,9 @@ def _expected_draw(B, seed=SEED):
 
 @pytest.mark.parametrize("K,B,atol", CASES)
 def test_projection_edges_gpu(K, B, atol):
-    from d4pg_amd.models import actor, critic
-    from d4pg_amd.ops import FusedEngine
-    dist = {"type": "categorical", "v_min": V_MIN, "v_max": V_MAX,
-            "n_atoms": K}
-    eng = FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                      capacity=N, v_min=V_MIN, v_max=V_MAX, gamma_n=GAMMA_N,
-                      tau=0.001, lr_actor=1e-4, lr_critic=1e-4, seed=SEED)
+    shape = kit.Shape(B, H, O, A, K)
+    eng = kit.engine(shape, kit.modules(shape, seed=K), capacity=N, seed=SEED)
     assert bool(eng.info().get("persistent", False)) == (B <= 256)
-    torch.manual_seed(K)
-    a = actor(O, A, hidden=H)
-    c = critic(O, A, dist, hidden=H)
-    eng.load_from_modules(a, copy.deepcopy(a), c, copy.deepcopy(c))
     rng = np.random.default_rng(K)
     r, d = orc.edge_rows(N, K, V_MIN, V_MAX, seed=K)
     eng.ingest(torch.from_numpy(rng.standard_normal((N, O)).astype("f")),

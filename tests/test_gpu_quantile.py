@@ -19,6 +19,9 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
+from _engine_kit import SLABS
+
 pytestmark = pytest.mark.gpu
 
 O, A = 5, 2
@@ -28,13 +31,8 @@ TAU, LR = 0.01, 1e-4
 PER_EPS = 1e-6
 N = 1024
 U2 = 2.0 ** -24
-LAYERS = ["fc1", "fc2", "fc2_2", "fc3"]
-SLABS = ["actor", "actor_target", "critic", "critic_target", "g_actor",
-         "g_critic", "m_actor", "v_actor", "m_critic", "v_critic"]
 BUFFERS = ["sum_tree", "min_tree", "bidx", "pri", "bw", "br", "bd", "ba",
            "bs2", "p_t", "m_proj", "q", "dlog"]
-INT_COUNTERS = ["beta_t", "adam_t_actor", "adam_t_critic", "rng_epoch",
-                "size", "pos"]
 
 SHAPES = {
     "persistent-8": dict(B=8, H=64, K=11),
@@ -51,24 +49,30 @@ def _dist(K):
     return {"type": "quantile", "n_atoms": K, "kappa": KAPPA}
 
 
-def _modules(H, K, seed=0):
-    from d4pg_amd.models import actor, critic
-    torch.manual_seed(seed)
-    a = actor(O, A, hidden=H)
-    c = critic(O, A, _dist(K), hidden=H)
+def _shape(name):
+    s = SHAPES[name]
+    return kit.Shape(s["B"], s["H"], O, A, s["K"], head="quantile",
+                     precision=s.get("gemm_precision", "fp32"), kappa=KAPPA,
+                     v_min=-1.0, v_max=1.0)
+
+
+def _modules(name):
+    a, at, c, _ = kit.modules(_shape(name), seed=SHAPES[name]["B"])
     with torch.no_grad():
         # quantiles spread over about [-2, 2] (the 3e-3 output init would
         # leave every u_ij of a row with the sign of r)
-        c.fc3.weight.normal_(0.0, 2.0 / math.sqrt(H))
+        c.fc3.weight.normal_(0.0, 2.0 / math.sqrt(SHAPES[name]["H"]))
         c.fc3.weight[0].zero_()
         c.fc3.bias[0] = 0.5
     ct = copy.deepcopy(c)
     with torch.no_grad():
         ct.fc3.bias[0] = 0.0
-    return a, copy.deepcopy(a), c, ct
+    return a, at, c, ct
 
 
 def _transitions(seed=0):
+    # its own generator: r and the mask of the reward atom are drawn BEFORE
+    # s, which the kit's s, a, r, s2, d order cannot reproduce
     rng = np.random.default_rng(seed)
     r = rng.uniform(-3, 3, N).astype("f")
     r[rng.random(N) < 0.5] = 0.5
@@ -78,29 +82,17 @@ def _transitions(seed=0):
             (rng.random(N) < 0.1).astype("f"))
 
 
-def _engine(name, mods, tr, seed=13, **kw):
-    from d4pg_amd.ops import FusedEngine
-    cfg = dict(SHAPES[name])
-    B, H, K = cfg.pop("B"), cfg.pop("H"), cfg.pop("K")
-    cfg.update(kw)
-    cfg.setdefault("dist", "quantile")
-    cfg.setdefault("kappa", KAPPA)
-    eng = FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                      capacity=N, v_min=-1.0, v_max=1.0, gamma_n=GAMMA_N,
-                      tau=TAU, lr_actor=LR, lr_critic=LR, per_eps=PER_EPS,
-                      seed=seed, **cfg)
-    eng.load_from_modules(*mods)
-    eng.ingest(*[torch.from_numpy(x) for x in tr])
-    return eng
+def _engine(name, mods, tr, **kw):
+    return kit.engine(_shape(name), mods, tr, capacity=N, gamma_n=GAMMA_N,
+                      tau=TAU, lr=LR, per_eps=PER_EPS, **kw)
 
 
 def _fresh(name, **kw):
-    s = SHAPES[name]
     # the data seed is chosen so that even the B = 8 batch of the first step
     # (PER draw of seed 13 over 1024 equal leaves) holds a done row and rows
     # with r = 0.5; test_row_formulas asserts the counts
-    mods = _modules(s["H"], s["K"], seed=s["B"])
-    tr = _transitions(seed=s["B"] + 2000)
+    mods = _modules(name)
+    tr = _transitions(seed=SHAPES[name]["B"] + 2000)
     return _engine(name, mods, tr, **kw), mods, tr
 
 
@@ -121,21 +113,10 @@ def _first_step(name):
 
 
 def _state(eng):
-    st = {"slab:" + n: eng.store_slab(n).numpy() for n in SLABS}
-    st.update({n: eng.read(n).numpy() for n in BUFFERS})
-    cnt = eng.counters()
-    st.update({"cnt:" + n: cnt[n] for n in INT_COUNTERS})
-    return st, cnt
+    return kit.snapshot(eng, BUFFERS)
 
 
-def _assert_same(x, y, what):
-    sx, cx = x
-    sy, cy = y
-    for k in sx:
-        assert np.array_equal(sx[k], sy[k]), f"{what}: {k} differs"
-    # the loss scalars accumulate through cross-workgroup fp32 atomics
-    for k in ("loss_critic", "loss_actor"):
-        assert cx[k] == pytest.approx(cy[k], rel=1e-5), f"{what}: {k}"
+_assert_same = kit.assert_bitwise
 
 
 # ---------------------------------------------------------------------------
@@ -212,62 +193,13 @@ def test_row_formulas_against_float64_oracle(name):
 # 2. against the eager oracle
 # ---------------------------------------------------------------------------
 
-def _pack(module, get):
-    parts = []
-    for n in LAYERS:
-        lin = getattr(module, n)
-        parts.append(get(lin.weight).t().contiguous().reshape(-1))
-        parts.append(get(lin.bias).reshape(-1))
-    return torch.cat(parts).detach().numpy()
-
-
-class Eager:
-    """Eager torch replica of the quantile train step on a given batch:
-    critic Adam, policy gradient through the UPDATED critic, actor Adam, both
-    soft updates."""
-
+class Eager(kit.Eager):
     def __init__(self, mods):
-        self.a, self.at, self.c, self.ct = [copy.deepcopy(m) for m in mods]
-        self.opt_c = torch.optim.Adam(self.c.parameters(), lr=LR)
-        self.opt_a = torch.optim.Adam(self.a.parameters(), lr=LR)
-
-    def step(self, s, act, r, s2, d, w=None):
-        from d4pg_amd.algo.quantile import (quantile_huber_loss,
-                                            quantile_targets)
-        s, act, r, s2, d = [torch.from_numpy(x) for x in (s, act, r, s2, d)]
-        w = torch.ones_like(r) if w is None else torch.from_numpy(w)
-        with torch.no_grad():
-            self.a2 = self.at(s2)
-            self.p_t = self.ct(s2, self.a2)
-            self.T = quantile_targets(self.p_t, r, d, GAMMA_N)
-        self.q = self.c(s, act)
-        loss_c = (w * quantile_huber_loss(self.q, self.T, KAPPA)).mean()
-        self.c.zero_grad()
-        loss_c.backward()
-        self.g_critic = _pack(self.c, lambda p: p.grad.clone())
-        self.opt_c.step()
-        pl = -self.c(s, self.a(s)).mean(dim=1).mean()
-        self.a.zero_grad()
-        pl.backward()
-        self.opt_a.step()
-        with torch.no_grad():
-            for tp, sp in zip(self.at.parameters(), self.a.parameters()):
-                tp.lerp_(sp, TAU)
-            for tp, sp in zip(self.ct.parameters(), self.c.parameters()):
-                tp.lerp_(sp, TAU)
+        super().__init__(mods, LR, TAU,
+                         head=kit.QuantileHead(GAMMA_N, KAPPA))
 
     def slabs(self):
-        out = {"actor": _pack(self.a, lambda p: p),
-               "actor_target": _pack(self.at, lambda p: p),
-               "critic": _pack(self.c, lambda p: p),
-               "critic_target": _pack(self.ct, lambda p: p),
-               "g_actor": _pack(self.a, lambda p: p.grad),
-               "g_critic": self.g_critic}
-        for tag, net, opt in (("actor", self.a, self.opt_a),
-                              ("critic", self.c, self.opt_c)):
-            out["m_" + tag] = _pack(net, lambda p: opt.state[p]["exp_avg"])
-            out["v_" + tag] = _pack(net, lambda p: opt.state[p]["exp_avg_sq"])
-        return out
+        return dict(super().slabs(), **self.grads())
 
 
 def _check_slabs(got, want, steps, tag):
@@ -381,28 +313,15 @@ def test_grad_clip_with_quantile():
 # ---------------------------------------------------------------------------
 
 def _agent(dist, seed=0):
-    from d4pg_amd.algo.d4pg import DDPG
-    return DDPG(3, 1, memory_size=4096, batch_size=64, critic_dist_info=dist,
-                n_steps=5, gamma=0.99, prioritized_replay=True, hidden=64,
-                device="cuda", backend="hip", seed=seed)
+    return kit.agent(dist, memory_size=4096, hidden=64, seed=seed)
 
 
-def _fill(agent, n=1000, seed=7):
-    rng = np.random.default_rng(seed)
-    for _ in range(n):
-        agent.replayBuffer.add(rng.standard_normal(3).astype("f"),
-                               rng.uniform(-1, 1, 1).astype("f"),
-                               rng.uniform(-3, 3),
-                               rng.standard_normal(3).astype("f"),
-                               float(rng.random() < 0.1))
+def _fill(agent, n=1000):
+    kit.fill_agent(agent, n, reward=lambda rng: rng.uniform(-3, 3),
+                   done=lambda rng: float(rng.random() < 0.1))
 
 
-def _flat_params(agent):
-    from d4pg_amd.ops import pack_net
-    agent.engine.sync_params_if_dirty()
-    return torch.cat([pack_net(agent.actor), pack_net(agent.critic),
-                      pack_net(agent.actor_target),
-                      pack_net(agent.critic_target)]).numpy()
+_flat_params = kit.flat_params
 
 
 def test_checkpoint_resume_bitwise_and_kind_mismatch():
@@ -424,8 +343,7 @@ def test_checkpoint_resume_bitwise_and_kind_mismatch():
         a2.train()
     np.testing.assert_array_equal(_flat_params(a2), ref)
 
-    cat = _agent({"type": "categorical", "v_min": -300.0, "v_max": 0.0,
-                  "n_atoms": 51}, seed=5)
+    cat = _agent(kit.CATEGORICAL, seed=5)
     with pytest.raises(ValueError, match="critic head"):
         cat.load_state_dict(st)
     # and the other way round

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
 import _oracles as orc
 
 pytestmark = pytest.mark.gpu
@@ -27,21 +28,13 @@ ALPHA = np.float64(np.float32(0.6))     # the engine holds per_alpha as float
 
 
 def _engine(capacity, seed=3):
-    from d4pg_amd.ops import FusedEngine
-    return FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                       capacity=capacity, v_min=V_MIN, v_max=V_MAX,
-                       gamma_n=0.99 ** 5, tau=0.001, lr_actor=1e-4,
-                       lr_critic=1e-4, seed=seed)
+    return kit.engine(kit.Shape(B, H, O, A, K), capacity=capacity, seed=seed)
 
 
 def _rows(rng, T):
     """T fresh random transitions: every call's rows differ from every
     other's, so a stale or mixed-up row cannot compare equal."""
-    return (rng.standard_normal((T, O)).astype("f"),
-            rng.uniform(-1, 1, (T, A)).astype("f"),
-            rng.uniform(-30, 0, T).astype("f"),
-            rng.standard_normal((T, O)).astype("f"),
-            (rng.random(T) < 0.3).astype("f"))
+    return kit.draw_rows(rng, O, A, T, p_done=0.3)
 
 
 def _ingest(eng, rows):

@@ -6,35 +6,21 @@ loader)."""
 
 import numpy as np
 import pytest
-import torch
+
+import _engine_kit as kit
 
 pytestmark = pytest.mark.gpu
 
 
 def _mk_agent(seed=0, batch_size=64):
-    from d4pg_amd.algo.d4pg import DDPG
-    return DDPG(3, 1, memory_size=8192, batch_size=batch_size,
-                critic_dist_info={"type": "categorical", "v_min": -300.0,
-                                  "v_max": 0.0, "n_atoms": 51},
-                n_steps=5, gamma=0.99, prioritized_replay=True,
-                device="cuda", backend="hip", seed=seed)
+    return kit.agent(memory_size=8192, batch_size=batch_size, seed=seed)
 
 
 def _fill(agent, n=2000, seed=7):
-    rng = np.random.default_rng(seed)
-    for _ in range(n):
-        agent.replayBuffer.add(rng.standard_normal(3).astype("f"),
-                               rng.uniform(-1, 1, 1).astype("f"),
-                               -rng.random(),
-                               rng.standard_normal(3).astype("f"), 0.0)
+    kit.fill_agent(agent, n, seed)
 
 
-def _flat_params(agent):
-    from d4pg_amd.ops import pack_net
-    agent.engine.sync_params_if_dirty()
-    return torch.cat([pack_net(agent.actor), pack_net(agent.critic),
-                      pack_net(agent.actor_target),
-                      pack_net(agent.critic_target)])
+_flat_params = kit.flat_params
 
 
 def test_engine_resume_bitwise():
@@ -62,7 +48,7 @@ def test_engine_resume_bitwise():
     for _ in range(5):
         a2.train()
     got = _flat_params(a2)
-    np.testing.assert_array_equal(got.numpy(), ref.numpy())
+    np.testing.assert_array_equal(got, ref)
     c1 = a1.engine.engine.counters()
     c2 = a2.engine.engine.counters()
     assert c1["adam_t_actor"] == c2["adam_t_actor"] == 10
@@ -94,4 +80,4 @@ def test_engine_resume_wide_batch_graph_path():
     eng2.train_steps(8, steps_per_graph=4)   # recapture with restored seed
     a2.engine.ddpg.train_steps_done += 8
     got = _flat_params(a2)
-    np.testing.assert_array_equal(got.numpy(), ref.numpy())
+    np.testing.assert_array_equal(got, ref)

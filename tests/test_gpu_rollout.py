@@ -6,50 +6,21 @@ random_process.py:4-21, n-step fold replay_memory.py:38-45."""
 
 import numpy as np
 import pytest
-import torch
+import _engine_kit as kit
+from _oracles import cpu_rollout
 
 pytestmark = pytest.mark.gpu
 
 O, A, H, K = 3, 1, 256, 51
-DIST = {"type": "categorical", "v_min": -300.0, "v_max": 0.0, "n_atoms": K}
 
 
 def make_engine(capacity, seed=0, batch=64):
-    from d4pg_amd.models import actor, critic
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K,
-                      batch=batch, capacity=capacity, v_min=-300.0,
-                      v_max=0.0, gamma_n=0.99 ** 5, tau=0.001,
-                      lr_actor=1e-4, lr_critic=1e-4, seed=seed)
-    torch.manual_seed(seed)
-    a = actor(O, A, hidden=H)
-    c = critic(O, A, DIST, hidden=H)
-    eng.load_from_modules(a, a, c, c)
-    return eng, a
-
-
-def cpu_rollout(net, th0, td0, M, n_steps, horizon, gamma=0.99):
-    """Oracle: VectorPendulum + VecNStep with the SAME start state and a
-    noiseless policy; returns transitions in the device emit order
-    (tick-major, env-minor)."""
-    from d4pg_amd.envs.vector import VecNStep, VectorPendulum
-    env = VectorPendulum(M, seed=0, horizon=horizon)
-    env.th = np.asarray(th0, np.float64).copy()
-    env.thdot = np.asarray(td0, np.float64).copy()
-    env.t = 0
-    fold = VecNStep(M, O, A, n_steps, gamma)
-    obs = env._obs()
-    outs = []
-    with torch.no_grad():
-        for t in range(horizon):
-            a = net(torch.from_numpy(obs)).numpy()
-            a = np.clip(a, -1.0, 1.0).astype(np.float32)
-            obs2, r, done = env.step(a)
-            out = fold.push(obs, a, r, obs2, done)
-            if out is not None:
-                outs.append(out)
-            obs = obs2
-    return [np.concatenate([o[i] for o in outs]) for i in range(5)]
+    """(engine, actor): one seed for the engine, the actor and, continuing
+    the actor's stream, the critic."""
+    return kit.producer_engine(
+        O, A, hidden=H, n_atoms=K, capacity=capacity, batch=batch, seed=seed,
+        v_min=-300.0, v_max=0.0, gamma_n=0.99 ** 5, lr=1e-4, actor_seed=seed,
+        critic_seed=None)
 
 
 def test_rollout_dynamics_and_fold_parity():

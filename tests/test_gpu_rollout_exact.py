@@ -14,12 +14,22 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
 import _oracles as orc
-from test_gpu_rollout import cpu_rollout, make_engine
+from _oracles import cpu_rollout
 
 pytestmark = pytest.mark.gpu
 
 ALPHA = np.float64(np.float32(0.6))     # the engine holds per_alpha as float
+
+
+def make_engine(capacity, seed=0, batch=64):
+    """(engine, actor) of test_gpu_rollout.py: one seed for the engine, the
+    actor and, continuing the actor's stream, the critic."""
+    return kit.producer_engine(
+        3, 1, hidden=256, n_atoms=51, capacity=capacity, batch=batch,
+        seed=seed, v_min=-300.0, v_max=0.0, gamma_n=0.99 ** 5, lr=1e-4,
+        actor_seed=seed, critic_seed=None)
 
 
 def _state(eng):

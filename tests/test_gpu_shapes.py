@@ -3,11 +3,11 @@
 each execution path — persistent (B<=256), row-block (256<B<=512), and
 MFMA (B>512) — all against the eager fp32 oracle."""
 
-import copy
-
 import numpy as np
 import pytest
 import torch
+
+import _engine_kit as kit
 
 pytestmark = pytest.mark.gpu
 
@@ -16,27 +16,12 @@ GAMMA_N = 0.99 ** 3
 
 def run_one_step(O, A, H, K, B, cap=4096, seed=3):
     from d4pg_amd.algo.projection import categorical_projection
-    from d4pg_amd.models import actor, critic
-    from d4pg_amd.ops import FusedEngine
-    dist = {"type": "categorical", "v_min": -100.0, "v_max": 50.0,
-            "n_atoms": K}
-    eng = FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                      capacity=cap, v_min=-100.0, v_max=50.0,
-                      gamma_n=GAMMA_N, tau=0.01, lr_actor=1e-4,
-                      lr_critic=1e-4, seed=seed)
-    torch.manual_seed(seed)
-    a = actor(O, A, hidden=H)
-    c = critic(O, A, dist, hidden=H)
-    at = copy.deepcopy(a)
-    ct = copy.deepcopy(c)
-    eng.load_from_modules(a, at, c, ct)
-    rng = np.random.default_rng(seed)
-    n = max(2 * B, 512)
-    eng.ingest(torch.from_numpy(rng.standard_normal((n, O)).astype("f")),
-               torch.from_numpy(rng.uniform(-1, 1, (n, A)).astype("f")),
-               torch.from_numpy(rng.uniform(-20, 5, n).astype("f")),
-               torch.from_numpy(rng.standard_normal((n, O)).astype("f")),
-               torch.from_numpy((rng.random(n) < 0.1).astype("f")))
+    shape = kit.Shape(B, H, O, A, K, v_min=-100.0, v_max=50.0)
+    a, at, c, ct = mods = kit.modules(shape, seed)
+    rows = kit.transitions(shape, max(2 * B, 512), seed, r_range=(-20, 5),
+                           p_done=0.1)
+    eng = kit.engine(shape, mods, rows, capacity=cap, seed=seed,
+                     gamma_n=GAMMA_N, tau=0.01)
     eng.step(1)
 
     s = torch.from_numpy(eng.read("bs").numpy())

@@ -14,82 +14,31 @@ value, and nothing precomputed may cross a launch boundary.
   3. q after a 4-step launch against torch on the stored pre-step state
 """
 
-import copy
-
 import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
+from _engine_kit import Shape
+
 pytestmark = pytest.mark.gpu
 
-V_MIN, V_MAX = -300.0, 0.0
-GAMMA_N = 0.99 ** 5
-TAU, LR = 0.001, 1e-4
 CAP, N = 4096, 1024
-SLABS = ["actor", "actor_target", "critic", "critic_target", "g_actor",
-         "g_critic", "m_actor", "v_actor", "m_critic", "v_critic"]
 BUFFERS = ["sum_tree", "min_tree", "bidx", "pri", "bw", "br", "bd", "ba",
            "bs2", "bs", "m_proj", "q", "p_t", "a2", "a_out", "dlog"]
-INT_COUNTERS = ["beta_t", "adam_t_actor", "adam_t_critic", "rng_epoch",
-                "size", "pos"]
 
 
-class Shape:
-    def __init__(self, B, H, O, A, K, prioritized=True):
-        self.B, self.H, self.O, self.A, self.K = B, H, O, A, K
-        self.prioritized = prioritized
-        self.dist = {"type": "categorical", "v_min": V_MIN, "v_max": V_MAX,
-                     "n_atoms": K}
-
-    def __repr__(self):
-        return (f"B{self.B}-H{self.H}-O{self.O}-A{self.A}-K{self.K}"
-                + ("" if self.prioritized else "-uniform"))
-
-    def modules(self, seed):
-        from d4pg_amd.models import actor, critic
-        torch.manual_seed(seed)
-        a = actor(self.O, self.A, hidden=self.H)
-        c = critic(self.O, self.A, self.dist, hidden=self.H)
-        return a, copy.deepcopy(a), c, copy.deepcopy(c)
-
-    def transitions(self, n, seed):
-        rng = np.random.default_rng(seed)
-        return (rng.standard_normal((n, self.O)).astype("f"),
-                rng.uniform(-1, 1, (n, self.A)).astype("f"),
-                rng.uniform(-30, 0, n).astype("f"),
-                rng.standard_normal((n, self.O)).astype("f"),
-                (rng.random(n) < 0.05).astype("f"))
-
-    def engine(self, mods, tr, seed=13):
-        from d4pg_amd.ops import FusedEngine
-        eng = FusedEngine(obs_dim=self.O, act_dim=self.A, hidden=self.H,
-                          n_atoms=self.K, batch=self.B, capacity=CAP,
-                          v_min=V_MIN, v_max=V_MAX, gamma_n=GAMMA_N, tau=TAU,
-                          lr_actor=LR, lr_critic=LR, seed=seed,
-                          prioritized=self.prioritized)
-        eng.load_from_modules(*mods)
-        eng.ingest(*[torch.from_numpy(x) for x in tr])
-        assert eng._persistent
-        return eng
+def _engine(shape, mods, tr):
+    eng = kit.engine(shape, mods, tr, capacity=CAP)
+    assert eng._persistent
+    return eng
 
 
 def _state(eng):
-    st = {"slab:" + n: eng.store_slab(n).numpy() for n in SLABS}
-    st.update({n: eng.read(n).numpy() for n in BUFFERS})
-    cnt = eng.counters()
-    st.update({"cnt:" + n: cnt[n] for n in INT_COUNTERS})
-    return st, cnt
+    return kit.snapshot(eng, BUFFERS)
 
 
-def _assert_same(x, y, what):
-    sx, cx = x
-    sy, cy = y
-    for k in sx:
-        assert np.array_equal(sx[k], sy[k]), f"{what}: {k} differs"
-    # the loss scalars accumulate through cross-workgroup fp32 atomics,
-    # whose order is not fixed: approximately equal only
-    for k in ("loss_critic", "loss_actor"):
-        assert cx[k] == pytest.approx(cy[k], rel=1e-5), f"{what}: {k}"
+_assert_same = kit.assert_bitwise
 
 
 SHAPES = [
@@ -108,9 +57,9 @@ SHAPES = [
 
 @pytest.mark.parametrize("shape", SHAPES, ids=repr)
 def test_multistep_launch_is_bitwise_single_steps(shape):
-    mods = shape.modules(seed=shape.B)
-    tr = shape.transitions(N, seed=shape.B)
-    x, y, z = (shape.engine(mods, tr) for _ in range(3))
+    mods = kit.modules(shape, seed=shape.B)
+    tr = kit.transitions(shape, N, seed=shape.B)
+    x, y, z = (_engine(shape, mods, tr) for _ in range(3))
     x.step(5)
     for _ in range(5):
         y.step(1)
@@ -128,12 +77,12 @@ def test_nothing_precomputed_crosses_a_launch():
     that launches step by step (which never runs the pipelined schedule)."""
     from d4pg_amd.ops import pack_net
     shape = Shape(64, 128, 5, 2, 51)
-    mods = shape.modules(seed=1)
-    a2, _, c2, _ = shape.modules(seed=2)    # differently seeded W2 / A2
+    mods = kit.modules(shape, seed=1)
+    a2, _, c2, _ = kit.modules(shape, seed=2)    # differently seeded W2 / A2
     assert not torch.equal(pack_net(c2), pack_net(mods[2]))
-    tr = shape.transitions(N, seed=1)
-    fresh = [torch.from_numpy(t) for t in shape.transitions(512, seed=99)]
-    x, y = shape.engine(mods, tr), shape.engine(mods, tr)
+    tr = kit.transitions(shape, N, seed=1)
+    fresh = [torch.from_numpy(t) for t in kit.transitions(shape, 512, seed=99)]
+    x, y = _engine(shape, mods, tr), _engine(shape, mods, tr)
     for eng, launches in ((x, ([3], [2])), (y, ([1] * 3, [1] * 2))):
         for n in launches[0]:
             eng.step(n)
@@ -156,9 +105,9 @@ def test_q_after_multistep_launch_is_the_last_steps_own():
     from d4pg_amd.models import critic
     from d4pg_amd.ops import unpack_net
     shape = Shape(64, 128, 3, 1, 51)
-    mods = shape.modules(seed=4)
-    tr = shape.transitions(N, seed=4)
-    eng, twin = shape.engine(mods, tr), shape.engine(mods, tr)
+    mods = kit.modules(shape, seed=4)
+    tr = kit.transitions(shape, N, seed=4)
+    eng, twin = _engine(shape, mods, tr), _engine(shape, mods, tr)
     eng.step(4)
     twin.step(3)
     c = critic(shape.O, shape.A, shape.dist, hidden=shape.H)

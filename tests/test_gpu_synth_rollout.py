@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
 import _oracles as orc
 import _synth_oracles as so
 from d4pg_amd.envs.vector import PhiloxProcNoise, VecNStep, VectorSynthetic
@@ -39,25 +40,16 @@ TWIN_F64_BOUND = 5e-5
 def _net(o, a, hidden=H):
     """Actor with its head scaled up from the 3e-3 init, so that actions
     spread over (-1, 1) instead of sitting at 0."""
-    from d4pg_amd.models import actor
-    torch.manual_seed(NET_SEED)
-    net = actor(o, a, hidden=hidden)
-    with torch.no_grad():
-        net.fc3.weight.mul_(60.0)
-    return net
+    return kit.producer_nets(o, a, DIST, hidden=hidden, actor_seed=NET_SEED,
+                             critic_seed=NET_SEED, head_gain=60.0)[0]
 
 
 def make_engine(o, a, capacity, prioritized=True, hidden=H, batch=64):
-    from d4pg_amd.models import critic
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=o, act_dim=a, hidden=hidden, n_atoms=K,
-                      batch=batch, capacity=capacity, v_min=-10.0, v_max=1.0,
-                      gamma_n=GAMMA ** 3, tau=0.001, lr_actor=1e-4,
-                      lr_critic=1e-4, seed=0, prioritized=prioritized)
-    torch.manual_seed(NET_SEED)
-    c = critic(o, a, DIST, hidden=hidden)
-    eng.load_from_modules(_net(o, a, hidden), _net(o, a, hidden), c, c)
-    return eng
+    return kit.producer_engine(
+        o, a, hidden=hidden, n_atoms=K, capacity=capacity, batch=batch,
+        seed=0, v_min=-10.0, v_max=1.0, gamma_n=GAMMA ** 3, lr=1e-4,
+        prioritized=prioritized, actor_seed=NET_SEED, critic_seed=NET_SEED,
+        head_gain=60.0)[0]
 
 
 def _twin(o, a, m, hor, act_high=1.0, proc_sigma=0.0, ep=1):
@@ -397,7 +389,6 @@ def test_uniform_replay_rows_equal_per_rows():
 # ---------------------------------------------------------------------------
 
 def test_refusals():
-    from d4pg_amd.ops import FusedEngine
     o, a, m, n, hor = 5, 2, 8, 3, 10
     vec = _twin(o, a, m, hor)
     eng = make_engine(o, a, m * (hor - n + 1) - 1)
@@ -420,9 +411,8 @@ def test_refusals():
         eng.rollout_run(1)
     with pytest.raises(RuntimeError, match="goal_rollout_alloc first"):
         eng.goal_rollout_run(1)
-    pend = FusedEngine(obs_dim=3, act_dim=1, hidden=H, n_atoms=K, batch=64,
-                       capacity=4096, v_min=-50.0, v_max=0.0, gamma_n=GAMMA,
-                       tau=0.001, lr_actor=1e-4, lr_critic=1e-4, seed=0)
+    pend = kit.engine(kit.Shape(64, H, 3, 1, K, v_min=-50.0), capacity=4096,
+                      seed=0, gamma_n=GAMMA)
     pend.rollout_alloc(8, 3, horizon=10)
     with pytest.raises(RuntimeError, match="synth_rollout_alloc first"):
         pend.synth_rollout_run(1)
@@ -434,17 +424,15 @@ def test_refusals():
 
 def _life_engine(o, like=None):
     """(o, 1) engine with an 11-atom critic; `like`: take its four slabs."""
-    from d4pg_amd.models import critic
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=o, act_dim=1, hidden=H, n_atoms=11, batch=64,
-                      capacity=64, v_min=-10.0, v_max=1.0,
-                      gamma_n=GAMMA ** 2, tau=0.001, lr_actor=1e-4,
-                      lr_critic=1e-4, seed=0)
+    kw = dict(hidden=H, n_atoms=11, capacity=64, seed=0, v_min=-10.0,
+              v_max=1.0, gamma_n=GAMMA ** 2, lr=1e-4)
     if like is None:
-        torch.manual_seed(NET_SEED)
-        c = critic(o, 1, dict(DIST, n_atoms=11), hidden=H)
-        eng.load_from_modules(_net(o, 1), _net(o, 1), c, c)
+        eng, _ = kit.producer_engine(o, 1, actor_seed=NET_SEED,
+                                     critic_seed=NET_SEED, head_gain=60.0,
+                                     **kw)
     else:
+        eng = kit.engine(kit.Shape(64, H, o, 1, 11, v_min=-10.0, v_max=1.0),
+                         capacity=64, seed=0, gamma_n=GAMMA ** 2)
         for name in ("actor", "actor_target", "critic", "critic_target"):
             eng.load_slab(name, like.store_slab(name))
     return eng

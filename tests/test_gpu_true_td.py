@@ -14,25 +14,41 @@ import copy
 
 import numpy as np
 import pytest
-import torch
 
-from test_gpu_per_exact import (ALPHA, DIST, GAMMA_N, H, K, O, A, SEED, V_MAX,
-                                V_MIN, _inject, _modules, _replay)
+import _engine_kit as kit
 
 pytestmark = pytest.mark.gpu
 
+# the shape, seed and injected replay of test_gpu_per_exact.py
+O, A, H, K = 5, 2, 128, 51
+V_MIN, V_MAX = -300.0, 0.0
+GAMMA_N = 0.99 ** 5
+ALPHA = float(np.float32(0.6))          # the engine holds per_alpha as float
+SEED = 21
 PER_EPS = 1e-6
 ATOL = 20 * 2.0 ** -24 * max(abs(V_MIN), abs(V_MAX))
 Z = np.linspace(V_MIN, V_MAX, K)            # float64 atoms
+_inject = kit.inject_replay
+
+
+def _shape(B=0):
+    return kit.Shape(B, H, O, A, K)
+
+
+DIST = _shape().dist
 
 
 def _engine(B, capacity, true_td=True):
-    from d4pg_amd.ops import FusedEngine
-    return FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                       capacity=capacity, v_min=V_MIN, v_max=V_MAX,
-                       gamma_n=GAMMA_N, tau=0.001, lr_actor=1e-4,
-                       lr_critic=1e-4, per_eps=PER_EPS, seed=SEED,
-                       true_td_priorities=true_td)
+    return kit.engine(_shape(B), capacity=capacity, seed=SEED,
+                      per_eps=PER_EPS, true_td_priorities=true_td)
+
+
+def _modules(seed=0):
+    return kit.modules(_shape(), seed)
+
+
+def _replay(size, seed=0):
+    return kit.per_replay(_shape(), size, seed)
 
 
 def _td64(m, q):

@@ -16,35 +16,47 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
+import _goal_oracles as go
 import _oracles as orc
-import test_gpu_multistep as ms
-from test_uniform_oracle import uniform_batch
+from _oracles import uniform_batch
 
 pytestmark = pytest.mark.gpu
 
+# the shape, replay size and hyper-parameters of test_gpu_multistep.py
 O, A, H, K = 5, 2, 128, 51
 V_MIN, V_MAX = -300.0, 0.0
 GAMMA_N = 0.99 ** 5
+TAU, LR = 0.001, 1e-4
+N = 512
 SEED = 21
-assert (O, A, H, K, V_MIN, V_MAX) == (ms.O, ms.A, ms.H, ms.K, ms.V_MIN,
-                                      ms.V_MAX)
+BUFFERS = ["sum_tree", "min_tree", "bidx", "pri", "bw", "br", "bd", "ba",
+           "bs2", "m_proj", "q"]
 
 
-def _engine(B, capacity, seed=SEED, **kw):
-    from d4pg_amd.ops import FusedEngine
-    kw.setdefault("prioritized", False)
-    return FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                       capacity=capacity, v_min=V_MIN, v_max=V_MAX,
-                       gamma_n=GAMMA_N, tau=ms.TAU, lr_actor=ms.LR,
-                       lr_critic=ms.LR, seed=seed, **kw)
+def _shape(B, prioritized=False):
+    return kit.Shape(B, H, O, A, K, prioritized=prioritized)
+
+
+def _engine(B, capacity, seed=SEED, prioritized=False, **kw):
+    return kit.engine(_shape(B, prioritized), capacity=capacity, seed=seed,
+                      **kw)
+
+
+def _modules(seed=0):
+    return kit.modules(_shape(0), seed)
+
+
+def _transitions(seed=0):
+    return kit.transitions(_shape(0), N, seed)
 
 
 def _rows(rng, T):
-    return (rng.standard_normal((T, O)).astype("f"),
-            rng.uniform(-1, 1, (T, A)).astype("f"),
-            rng.uniform(-30, 0, T).astype("f"),
-            rng.standard_normal((T, O)).astype("f"),
-            (rng.random(T) < 0.3).astype("f"))
+    return kit.draw_rows(rng, O, A, T, p_done=0.3)
+
+
+def _state(eng):
+    return kit.snapshot(eng, BUFFERS)
 
 
 def _ingest(eng, rows):
@@ -69,10 +81,7 @@ def _replay(eng):
 
 
 def _trained(B, mods, tr, **kw):
-    eng = _engine(B, ms.N, seed=13, **kw)
-    eng.load_from_modules(*mods)
-    _ingest(eng, tr)
-    return eng
+    return kit.engine(_shape(B), mods, tr, capacity=N, **kw)
 
 
 # ---------------------------------------------------------------------------
@@ -84,7 +93,7 @@ def _trained(B, mods, tr, **kw):
 @pytest.mark.parametrize("B", [64, 300, 640])
 def test_exact_draw(B, capacity, size):
     eng = _engine(B, capacity)
-    eng.load_from_modules(*ms._modules())
+    eng.load_from_modules(*_modules())
     rows = _rows(np.random.default_rng(capacity), size)
     _inject(eng, rows)
     s, a, r, s2, d = rows
@@ -112,43 +121,43 @@ def test_exact_draw(B, capacity, size):
 # B = 48, 64: tail-crew pre-sample; 80: under the actor Adam; 128: re-sample
 @pytest.mark.parametrize("B", [48, 64, 80, 128])
 def test_multistep_launch_matches_single_steps(B):
-    mods, tr = ms._modules(seed=B), ms._transitions(seed=B)
+    mods, tr = _modules(seed=B), _transitions(seed=B)
     x, y, z = (_trained(B, mods, tr) for _ in range(3))
     assert x._persistent and not x.info()["prioritized"]
     x.step(5)
-    ms._assert_bs_is_gathered(x, "step(5)")
+    kit.assert_bs_is_gathered(x, "step(5)")
     epochs = []
     for i in range(5):
         y.step(1)
-        ms._assert_bs_is_gathered(y, f"step(1) #{i + 1}")
+        kit.assert_bs_is_gathered(y, f"step(1) #{i + 1}")
         epochs.append(y.read("bidx").numpy())
     # every step drew with its own epoch (a pre-sample one epoch off shows
     # here as well as in the comparison below)
     for i, idx in enumerate(epochs):
-        assert np.array_equal(idx, uniform_batch(13, i + 1, B, ms.N))
-    ref = ms._state(y)
-    ms._assert_same(ms._state(x), ref, "step(5) vs 5 x step(1)")
+        assert np.array_equal(idx, uniform_batch(13, i + 1, B, N))
+    ref = _state(y)
+    kit.assert_bitwise(_state(x), ref, "step(5) vs 5 x step(1)")
     z.step(2)
     z.step(3)
-    ms._assert_bs_is_gathered(z, "step(2)+step(3)")
-    ms._assert_same(ms._state(z), ref, "step(2)+step(3) vs 5 x step(1)")
+    kit.assert_bs_is_gathered(z, "step(2)+step(3)")
+    kit.assert_bitwise(_state(z), ref, "step(2)+step(3) vs 5 x step(1)")
     assert np.array_equal(x.read("bidx").numpy(),
-                          uniform_batch(13, 5, B, ms.N))
+                          uniform_batch(13, 5, B, N))
     assert ref[0]["cnt:rng_epoch"] == ref[0]["cnt:beta_t"] == 5
 
 
 def test_graph_replay_matches_uncaptured_rowblock():
     B = 300
-    mods, tr = ms._modules(seed=B), ms._transitions(seed=B)
+    mods, tr = _modules(seed=B), _transitions(seed=B)
     x, y = _trained(B, mods, tr), _trained(B, mods, tr)
     assert not x._persistent
     x.step(6)
     y.train_steps(6, steps_per_graph=3)
     assert y._captured == 3
-    ms._assert_same(ms._state(x), ms._state(y), "step(6) vs graph 2 x 3")
+    kit.assert_bitwise(_state(x), _state(y), "step(6) vs graph 2 x 3")
     assert x.counters()["adam_t_critic"] == 6
     assert np.array_equal(x.read("bidx").numpy(),
-                          uniform_batch(13, 6, B, ms.N))
+                          uniform_batch(13, 6, B, N))
 
 
 # ---------------------------------------------------------------------------
@@ -157,12 +166,13 @@ def test_graph_replay_matches_uncaptured_rowblock():
 
 @pytest.mark.parametrize("B", [64, 300, 640])
 def test_step_parity_with_eager(B):
-    mods, tr = ms._modules(seed=B), ms._transitions(seed=B)
+    mods, tr = _modules(seed=B), _transitions(seed=B)
     eng = _trained(B, mods, tr)
     eng.step(1)
     idx = eng.read("bidx").numpy()
-    assert np.array_equal(idx, uniform_batch(13, 1, B, ms.N))
-    eager = ms.Eager(mods)
+    assert np.array_equal(idx, uniform_batch(13, 1, B, N))
+    eager = kit.Eager(mods, LR, TAU, head=kit.CategoricalHead(
+        V_MIN, V_MAX, GAMMA_N, K))
     eager.step(*[t[idx] for t in tr])
     # test_gpu_multistep.py's tolerances: the wide path's gradient bounds
     # (1e-4 absolute, 1e-3 of the slab's largest entry) and 6e-5 on the
@@ -187,14 +197,14 @@ def test_step_parity_with_eager(B):
 
 @pytest.mark.parametrize("B", [64, 300, 640])
 def test_is_weighting_is_a_no_op(B):
-    mods, tr = ms._modules(seed=B), ms._transitions(seed=B)
+    mods, tr = _modules(seed=B), _transitions(seed=B)
     out = []
     for flag in (True, False):
         eng = _trained(B, mods, tr, is_weighting=flag)
         eng.step(2)
         assert np.array_equal(eng.read("bw").numpy(), np.ones(B, np.float32))
-        out.append(ms._state(eng))
-    ms._assert_same(out[0], out[1], "is_weighting True vs False")
+        out.append(_state(eng))
+    kit.assert_bitwise(out[0], out[1], "is_weighting True vs False")
 
 
 # ---------------------------------------------------------------------------
@@ -203,7 +213,7 @@ def test_is_weighting_is_a_no_op(B):
 
 @pytest.mark.parametrize("B", [64, 300, 640])
 def test_no_trees(B):
-    mods, tr = ms._modules(), ms._transitions()
+    mods, tr = _modules(), _transitions()
     eng = _trained(B, mods, tr)
     info = eng.info()
     assert info["tree_cap"] == 0 and info["prioritized"] is False
@@ -219,7 +229,7 @@ def test_no_trees(B):
     # the priorities are still computed (and ignored)
     assert (eng.read("pri").numpy() > 0).all()
     # a PER engine of the same shape does keep them
-    assert _engine(B, ms.N, prioritized=True).info()["tree_cap"] == ms.N
+    assert _engine(B, N, prioritized=True).info()["tree_cap"] == N
 
 
 # ---------------------------------------------------------------------------
@@ -273,25 +283,18 @@ def test_synth_fill_rows_equal_per_engine():
 
 
 def test_pendulum_rollout_episode():
-    import test_gpu_rollout as ro
-    from d4pg_amd.models import actor, critic
-    from d4pg_amd.ops import FusedEngine
     M, N, HOR = 8, 2, 4
     cap = M * (HOR - N + 1)
-    torch.manual_seed(4)
-    net = actor(ro.O, ro.A, hidden=ro.H)
-    c = critic(ro.O, ro.A, ro.DIST, hidden=ro.H)
     rng = np.random.default_rng(11)
     th0 = rng.uniform(-np.pi, np.pi, M).astype(np.float32)
     td0 = rng.uniform(-1, 1, M).astype(np.float32)
     states = {}
     for prioritized in (True, False):
-        eng = FusedEngine(obs_dim=ro.O, act_dim=ro.A, hidden=ro.H,
-                          n_atoms=ro.K, batch=64, capacity=cap, v_min=-300.0,
-                          v_max=0.0, gamma_n=0.99 ** 5, tau=0.001,
-                          lr_actor=1e-4, lr_critic=1e-4, seed=4,
-                          prioritized=prioritized)
-        eng.load_from_modules(net, net, c, c)
+        # test_gpu_rollout.py's engine: one seed for the engine and the nets
+        eng, net = kit.producer_engine(
+            3, 1, hidden=256, n_atoms=51, capacity=cap, seed=4, v_min=-300.0,
+            v_max=0.0, gamma_n=0.99 ** 5, lr=1e-4, prioritized=prioritized,
+            actor_seed=4, critic_seed=None)
         eng.rollout_alloc(M, N, horizon=HOR, gamma=0.99, eps=0.0, seed=9)
         eng.rollout_set_state(th0, td0)
         env_steps, emitted = eng.rollout_run(1, reset=False, use_graph=False)
@@ -304,7 +307,7 @@ def test_pendulum_rollout_episode():
     assert eng.counters()["max_priority"] == 1.0
     # against the host twins, at test_gpu_rollout.py's tolerances
     s, a, r, s2, d = eng.replay_rows()
-    S, Aa, R, S2, D = ro.cpu_rollout(net, th0, td0, M, N, HOR)
+    S, Aa, R, S2, D = orc.cpu_rollout(net, th0, td0, M, N, HOR)
     assert s.shape == S.shape
     np.testing.assert_allclose(a, Aa, rtol=2e-4, atol=2e-4)
     np.testing.assert_allclose(s, S, rtol=2e-4, atol=2e-4)
@@ -318,23 +321,13 @@ def test_pendulum_rollout_episode():
 
 
 def test_goal_rollout_episode():
-    import test_gpu_goal_rollout as go
-    from d4pg_amd.models import critic
-    from d4pg_amd.ops import FusedEngine
     n, ratio = 1, 0.8
     assert (go.M, go.HOR) == (8, 10)
-    pos0, goal0 = go._starts()
+    pos0, goal0 = go.starts()
     states = {}
     for prioritized in (False, True):
-        eng = FusedEngine(obs_dim=go.O, act_dim=go.A, hidden=go.H,
-                          n_atoms=go.K, batch=64,
-                          capacity=go.episode_max(go.M, n, go.HOR),
-                          v_min=-50.0, v_max=0.0, gamma_n=go.GAMMA ** 3,
-                          tau=0.001, lr_actor=1e-4, lr_critic=1e-4,
-                          seed=go.NET_SEED, prioritized=prioritized)
-        torch.manual_seed(go.NET_SEED)
-        c = critic(go.O, go.A, go.DIST, hidden=go.H)
-        eng.load_from_modules(go._net(), go._net(), c, c)
+        eng = go.make_engine(go.episode_max(go.M, n, go.HOR),
+                             seed=go.NET_SEED, prioritized=prioritized)
         eng.goal_rollout_alloc(go.M, n, horizon=go.HOR, gamma=go.GAMMA,
                                speed=go.SPEED, tol=go.TOL, her_ratio=ratio,
                                eps=go.EPS, seed=go.SEED)
@@ -365,29 +358,12 @@ def test_goal_rollout_episode():
 # ---------------------------------------------------------------------------
 
 def _agent(seed=0, prioritized=False, **kw):
-    from d4pg_amd.algo.d4pg import DDPG
-    return DDPG(3, 1, memory_size=8192, batch_size=64,
-                critic_dist_info={"type": "categorical", "v_min": -300.0,
-                                  "v_max": 0.0, "n_atoms": 51},
-                n_steps=5, gamma=0.99, prioritized_replay=prioritized,
-                device="cuda", backend="hip", seed=seed, **kw)
+    return kit.agent(memory_size=8192, prioritized=prioritized, seed=seed,
+                     **kw)
 
 
-def _fill(agent, n, seed=7):
-    rng = np.random.default_rng(seed)
-    for _ in range(n):
-        agent.replayBuffer.add(rng.standard_normal(3).astype("f"),
-                               rng.uniform(-1, 1, 1).astype("f"),
-                               -rng.random(),
-                               rng.standard_normal(3).astype("f"), 0.0)
-
-
-def _flat_params(agent):
-    from d4pg_amd.ops import pack_net
-    agent.engine.sync_params_if_dirty()
-    return torch.cat([pack_net(agent.actor), pack_net(agent.critic),
-                      pack_net(agent.actor_target),
-                      pack_net(agent.critic_target)]).numpy()
+_fill = kit.fill_agent
+_flat_params = kit.flat_params
 
 
 def test_resume_bitwise_and_cross_mode_refusal():

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import _engine_kit as kit
+
 pytestmark = pytest.mark.gpu
 
 O, A, H, K = 17, 6, 128, 51
@@ -16,30 +18,14 @@ B = 1024
 GAMMA_N = 0.99 ** 5
 TAU = 0.001
 LR = 1e-4
-DIST = {"type": "categorical", "v_min": -300.0, "v_max": 0.0, "n_atoms": K}
 
 
 @pytest.fixture(scope="module")
 def wstepped():
-    from d4pg_amd.models import actor, critic
-    from d4pg_amd.ops import FusedEngine
-    eng = FusedEngine(obs_dim=O, act_dim=A, hidden=H, n_atoms=K, batch=B,
-                      capacity=8192, v_min=-300.0, v_max=0.0,
-                      gamma_n=GAMMA_N, tau=TAU, lr_actor=LR, lr_critic=LR,
-                      seed=11)
-    torch.manual_seed(5)
-    a = actor(O, A, hidden=H)
-    c = critic(O, A, DIST, hidden=H)
-    at = copy.deepcopy(a)
-    ct = copy.deepcopy(c)
-    eng.load_from_modules(a, at, c, ct)
-    rng = np.random.default_rng(7)
-    n = 4096
-    eng.ingest(torch.from_numpy(rng.standard_normal((n, O)).astype("f")),
-               torch.from_numpy(rng.uniform(-1, 1, (n, A)).astype("f")),
-               torch.from_numpy(rng.uniform(-30, 0, n).astype("f")),
-               torch.from_numpy(rng.standard_normal((n, O)).astype("f")),
-               torch.from_numpy((rng.random(n) < 0.05).astype("f")))
+    shape = kit.Shape(B, H, O, A, K)
+    a, at, c, ct = mods = kit.modules(shape, seed=5)
+    eng = kit.engine(shape, mods, kit.transitions(shape, 4096, seed=7),
+                     capacity=8192, seed=11)
     eng.step(1)
     out = {name: eng.read(name) for name in
            ["bs", "ba", "br", "bs2", "bd", "q", "p_t", "a2", "m_proj",

@@ -25,7 +25,8 @@ import numpy as np
 import pytest
 import torch
 
-from _wide_gemm import (CONFIGS, LR, SLABS, Net, _engine, _gemm, _ks_dw,
+import _engine_kit as kit
+from _wide_gemm import (CONFIGS, LR, Net, _engine, _gemm, _ks_dw,
                         _modules, _rows, check_actor_phase,
                         check_critic_phase, run_phased)
 
@@ -123,13 +124,15 @@ def test_operands_round_to_nearest_even():
 # ---------------------------------------------------------------------------
 
 def _slabs(eng):
-    return {n: eng.store_slab(n) for n in SLABS}
+    """The ten slabs as int32 words: -0.0 and NaN payloads count too."""
+    st, _ = kit.snapshot(eng, [], counters=[])
+    return {k: v.view(np.int32) for k, v in st.items()}
 
 
 def _assert_slabs_equal(x, y, what):
-    for n in SLABS:
-        assert torch.equal(x[n].view(torch.int32), y[n].view(torch.int32)), \
-            f"{what}: slab {n} differs"
+    assert x.keys() == y.keys()
+    for k in x:
+        assert np.array_equal(x[k], y[k]), f"{what}: {k} differs"
 
 
 def test_two_runs_are_bitwise_equal():

@@ -3,25 +3,15 @@
 Probe `probe` of step-epoch `epoch` takes the first two philox words of the
 PER draw's own stream, x = (w0 << 32) | w1, and lands on slot
 floor(x * n / 2^64) of the n occupied rows.  The product is exact in Python
-integers; the kernel takes the high half of a 64 x 64-bit multiply.  The GPU
-tests (test_gpu_uniform_replay.py) import `uniform_index` from here.
+integers; the kernel takes the high half of a 64 x 64-bit multiply.  The
+oracle is `uniform_batch` of tests/_oracles.py, which the GPU tests
+(test_gpu_uniform_replay.py) use too.
 """
 
 import numpy as np
 import pytest
 
-from _oracles import philox4x32_10
-
-
-def uniform_index(seed, epoch, probe, n):
-    w = philox4x32_10(seed, epoch, probe)
-    x = (w[0] << 32) | w[1]
-    return (x * int(n)) >> 64
-
-
-def uniform_batch(seed, epoch, B, n):
-    return np.array([uniform_index(seed, epoch, i, n) for i in range(B)],
-                    np.int64)
+from _oracles import philox4x32_10, uniform_batch
 
 
 DRAWS = 10 ** 4
